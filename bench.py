@@ -2,21 +2,26 @@
 """Benchmark: WaveNet training step (forward + masked xent + backward + TF1 Adam) on
 MI355X with synthetic 16 kHz µ-law input dealt by the reference's slicing semantics.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps of
+the headline configuration and prints the result line; `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  Everything else below -- the live kernel probes and
+rooflines, C1 / C3 / C4 / C5 and the CPU baselines -- is measured only with `--full`.
+
 * N = 1: arch3 (par/arch3.json), B = 8 streams x T = 4096 (BASELINE.json configs[1], SURVEY
-  §8 C2) is the headline line; the same run adds C4 (arch5, B = 32), the per-GPU share of C5
+  §8 C2) is the headline line; a --full run adds C4 (arch5, B = 32), the per-GPU share of C5
   (arch5, B = 8, one GPU), C1 (arch1, B = 2, T = 512, forward + loss) and C3 (cached
   generation, arch3, B = 10) as sub-objects, each with its CPU baseline where one applies.
 * N > 1: data-parallel (one process per GPU, RCCL all-reduce of the flat gradient bucket +
   loss stats), per-GPU work fixed, so scaling is weak.  The headline line keeps the N = 1
   configuration per GPU (arch3, B = 8 per GPU) so that value(N) / value(1) is a true
-  weak-scaling ratio; the same run then measures C5 -- arch5 at 8 streams per GPU, B = 8N
+  weak-scaling ratio; a --full run then measures C5 -- arch5 at 8 streams per GPU, B = 8N
   in total (BASELINE configs[4] at N = 8) -- as the ``c5`` sub-object, whose one-GPU
   reference is the N = 1 line's ``c5_per_gpu``.  ``python bench.py --gpus N`` without
   torch.distributed.run spawns the N ranks itself (before anything touches the GPU; no
   exec); under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE like any worker.
 
 Prints ONE JSON line (rank 0).  `value` = audio samples/s for the whole job (all ranks):
-N·B·T / step time.  `roofline` is for the dominant kernel, timed live with HIP events
+N·B·T / step time.  With --full, `roofline` is for the dominant kernel, timed live with HIP events
 recorded by the plan around that launch on the plan's stream; `roofline_dilconv` is the
 same for the residual-layer forward kernel (the dilated-conv path, HBM-bound).
 `cpu_baseline` times the CPU restatement (oracle/, numpy fp32; the reference's TF-CPU path
@@ -356,11 +361,16 @@ class TrainBench:
         torch.cuda.synchronize()
         self.plan = self.net._plan(T)
 
-    def step(self, i):
+    def step(self, i, keep=None):
+        """`keep`: (gradient, stats) buffers that receive the step's reduced gradient and loss
+        stats before the optimizer kernel consumes and clears them (--dump-outputs, last step)."""
         q, mel, ids = self.ring[i % len(self.ring)]
         self.net.forward(q, mel, ids, backward=self.backward)
         if self.backward:
             self.dp.reduce_grads(self.net)
+            if keep:
+                keep[0].copy_(self.net.grad_flat)
+                keep[1].copy_(self.net.stats)
             self.opt.apply(self.net)
 
     def probe(self, name):
@@ -372,9 +382,11 @@ class TrainBench:
         _lib.check(self.net.lib.lbwn_plan_probe(self.plan, name.encode(), s.cuda_event, e.cuda_event))
         return s, e
 
-    def run(self, steps, warmup, probes=None, probe_mode='auto'):
+    def run(self, steps, warmup, probes=None, probe_mode='auto', keep_last=False):
         """Warm up (one probe per warmup step to find the dominant kernel), then time
-        exactly `steps` steps between barrier + synchronize pairs; max over ranks."""
+        exactly `steps` steps between barrier + synchronize pairs; max over ranks.
+        `keep_last`: the last timed step copies its gradient and stats to self.kept (two device
+        copies into buffers allocated here, before the timed region)."""
         import torch
         import torch.distributed as dist
         from lbwn import _lib
@@ -406,6 +418,7 @@ class TrainBench:
                 e.record()
                 pairs[i] = (dom if k % 2 == 0 else 'layer_fwd', s, e)
         pending = []
+        self.kept = (torch.empty_like(self.net.grad_flat), torch.empty_like(self.net.stats)) if keep_last else None
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -415,7 +428,7 @@ class TrainBench:
                 name, s, e = pairs[i]
                 _lib.check(self.net.lib.lbwn_plan_probe(self.plan, name.encode(), s.cuda_event, e.cuda_event))
                 pending.append((name, (s, e)))
-            self.step(warmup + i)
+            self.step(warmup + i, keep=self.kept if i == steps - 1 else None)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -571,6 +584,34 @@ def sub_bench(arch_file, B, T, dp, steps, warmup, gc=None, backward=True, label=
     return out
 
 
+DUMP_LIMIT = 60 * 10 ** 6    # bytes of array data per --dump-outputs directory (headers included: under 64 MB)
+
+
+def dump_outputs(path, net, grads, stats):
+    """--dump-outputs: what a caller of the timed path holds after its last step (WaveNetTrain.build
+    + AdamOptimizer.apply_gradients), as float32 <name>.npy: `grads` and `stats`, the step's raw
+    gradient (flat, ParamLayout order, summed over ranks) and (Σxent, n_valid, Σ|argmax diff|, -)
+    as kept before the optimizer kernel cleared them; `xent`, its mean cross-entropy
+    Σxent / n_valid; `params`, the parameters after the Adam update; `save`, the lookback SAVE
+    rows.  (The dealer masks the first receptive field of every stream, 5115 positions for arch3,
+    so at the headline shape ring entry 0 -- the
+    last step's slice when steps + warmup = 1 mod 8 -- has no valid sample: its grads, stats and
+    xent are exact zeros, while params and save still carry every earlier step.)  An array over its
+    share of DUMP_LIMIT is written as a fixed seeded sample of its
+    elements (ascending flat indices, the same for every run of the same shapes)."""
+    import torch
+    torch.cuda.synchronize()
+    arrs = {'xent': (stats[0] / torch.clamp(stats[1], min=1.0)).reshape(1), 'stats': stats, 'grads': grads,
+            'params': net.flat, 'save': net.save_flat}
+    share = DUMP_LIMIT // len(arrs) // 4
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrs.items():
+        a = t.detach().float().cpu().numpy().reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -579,10 +620,16 @@ def parse_args(argv=None):
     ap.add_argument('--arch', default=None, help='default: par/arch3.json (C2 per GPU); C5 (arch5) rides along')
     ap.add_argument('--batch', type=int, default=8, help='streams per GPU')
     ap.add_argument('--slice', type=int, default=4096)
+    ap.add_argument('--gc', type=int, default=None, help='--num-global-cond for GC archs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed (xent, stats, grads, params, '
+                         'save) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='beyond the headline: the live kernel probes and rooflines, cached generation (C3), the '
+                         'C1 / C4 / C5 sub-benchmarks and the CPU baselines; the options below apply to it')
     ap.add_argument('--probe', default='auto')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--gc', type=int, default=None, help='--num-global-cond for GC archs')
     ap.add_argument('--no-gen', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the C1 / C4 / C5 sub-benchmarks')
     ap.add_argument('--gen-seconds', type=float, default=3.0)
@@ -683,7 +730,11 @@ def main(argv=None):
     B, T = args.batch, args.slice
     tb = TrainBench(arch, B, T, dp)
     net = tb.net
-    ms, dom, samples, warm_t = tb.run(args.steps, args.warmup, probes=cands(), probe_mode=args.probe)
+    # a plain run times the steps and nothing else; the live kernel probes ride along under --full
+    ms, dom, samples, warm_t = tb.run(args.steps, args.warmup, probes=cands() if args.full else None,
+                                      probe_mode=args.probe, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, *tb.kept)
     value = world * B * T / (ms / 1000.0)
     cid = {'arch3.json': 'C2' + (' per GPU' if world > 1 else ''),
            'arch5.json': 'C5' if B == 8 and world > 1 else 'arch5'}.get(os.path.basename(arch_file), 'custom')
@@ -706,10 +757,17 @@ def main(argv=None):
                    'arch': name, 'batch_per_gpu': B, 'global_batch': world * B,
                    'slice_sz': T, 'parallelism': 'dp%d' % world, 'world_size_seen': dist.get_world_size()
                    if dist.is_initialized() else 1},
-        'roofline': tb.roof(dom, samples[dom]),
-        'roofline_dilconv': tb.roof('layer_fwd', samples['layer_fwd']),
-        'warmup_probe_ms': warm_t,
     }
+    if not args.full:
+        tb.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+    out['roofline'] = tb.roof(dom, samples[dom])
+    out['roofline_dilconv'] = tb.roof('layer_fwd', samples['layer_fwd'])
+    out['warmup_probe_ms'] = warm_t
     if world == 1 and not args.no_gen and arch['n_lc_out'] == 0:
         out['gen'] = bench_gen(net, arch, B=10, seconds=args.gen_seconds)
         if not args.no_cpu_baseline:

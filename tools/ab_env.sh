@@ -16,7 +16,7 @@ for round in 1 2; do
   for A in "${ARMS[@]}"; do
     i=$((i + 1))
     O=gpurun_out/abe_${TAG}_${i}_$round.json
-    env $A timeout -k 10 200 python bench.py --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i ($A) failed"; tail -5 $O.err; exit 1; }
+    env $A timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i ($A) failed"; tail -5 $O.err; exit 1; }
     python - "$O" "$round" "$i" "$A" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -17,9 +17,9 @@ for round in 1 2; do
     i=$((i + 1))
     O=gpurun_out/ab_${TAG}_${i}_$round.json
     if [ "$A" = default ]; then
-      timeout -k 10 150 python bench.py --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i failed"; tail -5 $O.err; exit 1; }
+      timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i failed"; tail -5 $O.err; exit 1; }
     else
-      timeout -k 10 150 python tools/with_lib.py "$A" bench.py --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i ($A) failed"; tail -5 $O.err; exit 1; }
+      timeout -k 10 150 python tools/with_lib.py "$A" bench.py --full --no-cpu-baseline --no-extras --no-gen "${BARGS[@]}" > $O 2> $O.err || { echo "arm $i ($A) failed"; tail -5 $O.err; exit 1; }
     fi
     python - "$O" "$round" "$i" "$A" <<'PY'
 import json, sys

@@ -11,7 +11,9 @@ if [ "$2" != "skip-tests" ]; then
   bash tools/gpu_tests.sh $TAG || exit 1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1 || { tail -5 gpurun_out/smoke_$TAG.log; exit 1; }
 fi
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -20 gpurun_out/bench_$TAG.err; exit 1; }
+BOUT=${BOUT:-bench_out}    # where the full bench line goes
+mkdir -p $BOUT
+timeout -k 10 600 python bench.py --full > $BOUT/bench_$TAG.json 2> $BOUT/bench_$TAG.err || { tail -20 $BOUT/bench_$TAG.err; exit 1; }
 echo bench ok
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o run -- python bench.py --steps 10 --no-gen --no-cpu-baseline --no-extras > gpurun_out/prof_$TAG.log 2>&1 || exit 1
 S=$(find gpurun_out/prof_$TAG -name '*kernel_stats.csv' | head -1)
