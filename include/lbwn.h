@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LBWN_ABI_VERSION 2
+#define LBWN_ABI_VERSION 3
 
 /* par/arch*.json after normalisation (tmodel.py:10-23, arch.py:31-103). */
 typedef struct lbwn_arch {
@@ -128,7 +128,12 @@ int lbwn_adam_tf1(float* params, const float* grads, float* m, float* v, int64_t
 
 /* ---- cached autoregressive generation (imodel.WaveNetGen, imodel.py:7-303) ------------ */
 typedef struct lbwn_gen_plan lbwn_gen_plan;
-/* B streams, outputs for up to max_steps samples, teacher vector up to max_teacher codes. */
+/* B streams, outputs for up to max_steps samples, teacher vector up to max_teacher codes.
+ * Archs with local conditioning (n_lc_out > 0; ABI 3) take the training plan's limits (1..8
+ * upsample stages, strides >= 1, n_lc_in and n_lc_out multiples of 4; else EINVAL) and carve the
+ * upsampled mel, the upsample stages' scratch and a ring of projected per-step LC terms of NC
+ * steps (default 64; env LBWN_GEN_LC_CHUNK=<integer 1..4096> at plan creation overrides it,
+ * anything else is EINVAL).  NC bounds the ring's size (NC·L·B·256 bytes), not the run length. */
 int lbwn_gen_plan_create(const lbwn_arch* arch, int batch_sz, int64_t max_steps, int64_t max_teacher,
                          lbwn_gen_plan** out);
 void lbwn_gen_plan_destroy(lbwn_gen_plan* plan);
@@ -136,7 +141,10 @@ size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* plan);
 /* "samples" int32 [B][max_steps] (drawn µ-law codes), "wav" fp32 [B][max_steps]
  * (mu_decode of the draws, imodel.py:181-182), "logits" [B][Q] (last step), "step" int64,
  * "rings" (lookback state, SAVE layout), "teacher" int32, "status" int32 (0; 5 when a persistent
- * hand-off timed out). */
+ * hand-off timed out); LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
+ * ([B][rows][n_lc_out] bytes), of which lbwn_gen_set_mel fills the first B·n_frames·hop rows
+ * densely as [B][n_frames·hop][n_lc_out], and "lccond" fp32 [NC][L][B][64] (slot = step mod NC;
+ * columns: signal 0..31 | gate 32..63, zero past n_dil). */
 int lbwn_gen_tensor(const lbwn_gen_plan* plan, const char* name, size_t* offset, size_t* bytes);
 /* Reset the state (zero lookback rings = imodel's zero-initialised buffers, step 0 input =
  * zero vector), load the teacher codes (device int32, may be NULL) and GC ids (device
@@ -146,10 +154,22 @@ int lbwn_gen_tensor(const lbwn_gen_plan* plan, const char* name, size_t* offset,
  * reference's tf.multinomial, imodel.py:179, is TF-RNG and not reproducible). */
 int lbwn_gen_start(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* gc_ids,
                    const int* teacher, int64_t n_teacher, uint64_t seed, int pre_bias, void* stream);
+/* Load the local conditioning of an LC plan (ABI 3): mel is device fp32 [B][n_frames][n_lc_in];
+ * runs the upsample stack of the training plan (transposed convolutions, kernel = stride) once
+ * into "lc".  Call after lbwn_gen_start (which clears the loaded state) and before the first
+ * lbwn_gen_run.  Generation step i (input: sample i-1, output: sample i) is training position
+ * i-1, so it is conditioned on lc row r(i) = min(max(i-1, 0), n_frames·hop - 1): step 0 uses row
+ * 0 and steps past the mel reuse its last row.  EINVAL before any launch when the arch has no
+ * LC, mel is NULL, n_frames < 1 or n_frames·hop exceeds the plan's rows. */
+int lbwn_gen_set_mel(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const float* mel,
+                     int64_t n_frames, void* stream);
 /* Generate n_steps more samples for every stream (the tf.while_loop body, imodel.py:214-272).
  * Device-resident step counter: the launches are graph-capturable and replayable.  Persistent
  * plans (lbwn_gen_is_persistent) run the whole call as ONE launch whose blocks must all be
- * resident: nothing else may occupy the device's CUs meanwhile. */
+ * resident: nothing else may occupy the device's CUs meanwhile.  LC plans split the call into
+ * sub-runs of <= NC steps, each a projection launch (the sub-run's LC terms into "lccond") followed
+ * by the step launches (persistent plans: one persistent launch per sub-run); EINVAL before any
+ * launch when no mel is loaded. */
 int lbwn_gen_run(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, int n_steps, void* stream);
 /* 1 when the plan runs the persistent one-launch form (groups of <= 16 streams, each with its
  * own 32 head blocks, while every block fits on the device: B <= 80 on 256 CUs; layer/head sizes fit;

@@ -14,9 +14,13 @@
 //     ring by LDS-DMA), gen_gemv × 3 (K-split row-vector products with deterministic partial
 //     sums: skip = z_cat·SKIPcat, h = relu(relu(skip + Σb)·POST1 + b1), logits = h·POST2) and
 //     gen_sample (Σ partials + b2, the draw)
+// Local conditioning (no counterpart in imodel.py; tmodel.py:155-160): lbwn_gen_set_mel upsamples
+// the mel once, gen_lc_proj_kernel projects it for the next <= NC steps into a cond ring, and the
+// step kernels' loaders DMA that step's row into the fourth bias row of each layer's LDS slot.
 // Both draw with the same wave-level inverse-CDF code: u = hash(seed, stream, step), µ-law
 // decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -78,6 +82,7 @@ struct WaveK {
   float* rings; float* zcat; const long long* step; const int* code;
   int B, L, nbl, Cr, Cd, pre_bias;
   long long* trace;   // non-null (LBWN_GEN_TRACE set at plan creation): stream 0's cycle stamps
+  const float* lccond; int NC;   // LC plans: the cond ring [NC][L][B][64] (gen_lc_proj_kernel)
 };
 
 LBWN_DEV float dot4(const floatx4& w, const floatx4& x, float acc) {
@@ -105,6 +110,9 @@ LBWN_DEV void dma4(const float* src, float* lds_dst) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
 }
 
+// LC: the slot's fourth row is this step's projected LC term lccond[t mod NC][l][b] instead of
+// the zero row (same DMA count), added to the conv bias beside the GC row
+template <bool LC>
 __global__ __launch_bounds__(512) void gen_wave_kernel(WaveK a) {
   __shared__ __attribute__((aligned(16))) float sm[G_LDS];
   float* RING = sm;                  // [G_NS][G_SLOT]
@@ -115,6 +123,7 @@ __global__ __launch_bounds__(512) void gen_wave_kernel(WaveK a) {
   if (wid >= 4) {   // ---- loader waves
     const int lw = wid - 4;
     const float* zeros = a.img + GI_WR + 128;   // the image's zero row (layer 0)
+    const float* lcrow = LC ? a.lccond + ((long)(int)(t % a.NC) * L * a.B + b) * 64 : zeros;
     // (a) taps: pair q = layers 2q, 2q+1 (lane half h) by loader q % 4; d is a power of two,
     // slot = t & (d-1); ring offsets carried in scalars (no integer division)
     {
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(512) void gen_wave_kernel(WaveK a) {
       }
       const float* row = lw < 2 ? src + GI_WR + lw * 64
                        : lw == 2 ? (a.gc_proj ? a.gc_proj + ((long)l * a.B + b) * 64 : zeros)
-                                 : zeros;
+                                 : (LC ? lcrow + (long)l * a.B * 64 : zeros);
       dma4(row + lane, dst + GI_WR + lw * 64);
     };
     for (int l = 0; l < G_NS - 1 && l < L; ++l) issue(l);
@@ -204,7 +213,8 @@ __global__ __launch_bounds__(512) void gen_wave_kernel(WaveK a) {
       wv[m] = *(const floatx4*)(S + (w * 4 + m) * 256 + lane * 4);
       xv[m] = *(const floatx4*)((m < 2 ? XP + l * 32 : XW) + 8 * kq + 4 * (m & 1));
     }
-    const float bco = S[GI_WR + o] + S[GI_WR + 128 + o];
+    float bco = S[GI_WR + o] + S[GI_WR + 128 + o];
+    if (LC) bco += S[GI_WR + 192 + o];
     __builtin_amdgcn_sched_barrier(0);
     const int d = 1 << bl;
     // x_l[t] into the ring (wave w stores channels 8w..8w+7)
@@ -621,6 +631,7 @@ struct PersistK {
   int Bg;                   // streams per group: block g·(Bg + P_NH) + r is group g's chain block r < Bg
                             // (stream g·Bg + r) or head block r - Bg; groups hand off only inside
   long long* gstep;         // step counters of groups 1.. (group 0's is *step, the plan's "step")
+  const float* lccond; int NC;   // LC plans: the cond ring [NC][L][B][64]; a run is <= NC steps
 };
 
 // poll granules base[off + i·stride], i < nv (N at most; the rest re-read granule nv-1), until
@@ -666,6 +677,7 @@ LBWN_DEV void dma4_sc1(const float* src, float* lds_dst) {
 }
 
 
+template <bool LC>
 LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* stepc, long long* trace) {
   float* RING = sm;                  // [G_NS][G_SLOT]
   float* XP = sm + G_NS * G_SLOT;    // [L][32] dilated taps of this step
@@ -700,11 +712,16 @@ LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* step
     // the layer and ring slot of the next issue, advanced with wrap-around: g mod L and g mod G_NS
     // of a 64-bit g were two long divisions per layer on the loaders' path to every barrier
     int iss_l = 0, iss_slot = 0;
+    int iss_c = LC ? (int)(t0 % a.NC) : 0;   // cond-ring slot of the issued layer's step (t mod NC)
     auto issue = [&](long /*g: layer iss_l, slot iss_slot*/) {   // weights of global layer g into slot g mod G_NS
       const int l = iss_l;
       const float* src = a.img + (long)l * GIMG;
       float* dst = RING + iss_slot * G_SLOT;
+      const int cs = iss_c;
       iss_l = (iss_l + 1 == L) ? 0 : iss_l + 1;
+      if constexpr (LC) {
+        if (iss_l == 0) iss_c = (iss_c + 1 == a.NC) ? 0 : iss_c + 1;
+      }
       iss_slot = (iss_slot + 1 == G_NS) ? 0 : iss_slot + 1;
 #pragma unroll
       for (int p = 0; p < G_PIECES; ++p) {
@@ -714,6 +731,9 @@ LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* step
       const float* row = lw < 2 ? src + GI_WR + lw * 64
                        : lw == 2 ? (a.gc_proj ? a.gc_proj + ((long)l * a.B + b) * 64 : zeros)
                                  : zeros;
+      if constexpr (LC) {
+        if (lw == 3) row = a.lccond + (((long)cs * L + l) * a.B + b) * 64;
+      }
       dma4(row + lane, dst + GI_WR + lw * 64);
     };
     taps(t0);
@@ -823,7 +843,8 @@ LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* step
         wv[mm] = *(const floatx4*)(S + (w * 4 + 2 + mm) * 256 + lane * 4);
         xv[mm] = *(const floatx4*)(XW + 8 * kq + 4 * mm);
       }
-      const float bco = S[GI_WR + o] + S[GI_WR + 128 + o];
+      float bco = S[GI_WR + o] + S[GI_WR + 128 + o];
+      if (LC) bco += S[GI_WR + 192 + o];
       // (round 2: reading ALL of layer l+1's conv operands right after barrier l, and this layer's
       // residual weights ahead of the conv, measured 38.0 -> 38.9 us per step; what is kept is
       // the dilated half after the barrier and the residual weights just before the z write)
@@ -1048,13 +1069,14 @@ LBWN_DEV void persist_head(const PersistK& a, int m, float* sm, int b0, int B, l
   }
 }
 
+template <bool LC>
 __global__ __launch_bounds__(512) void gen_persist_kernel(PersistK a) {
   __shared__ __attribute__((aligned(16))) float sm[G_LDS];
   const int per = a.Bg + P_NH, g = blockIdx.x / per, r = blockIdx.x % per;
   const int b0 = g * a.Bg, Bg = min(a.Bg, a.B - b0);
   long long* stepc = g ? a.gstep + (g - 1) : a.step;
   long long* trace = g ? nullptr : a.trace;
-  if (r < Bg) persist_chain(a, sm, b0 + r, stepc, trace);
+  if (r < Bg) persist_chain<LC>(a, sm, b0 + r, stepc, trace);
   else if (r >= a.Bg) persist_head(a, r - a.Bg, sm, b0, Bg, stepc, trace);
   // (a ragged last group leaves chain slots r in [Bg, a.Bg) idle)
 }
@@ -1074,6 +1096,70 @@ __global__ void gen_gc_proj_kernel(const float* emb, const float* gsig, const fl
     out[((long)l * B + b) * 64 + o] = s;
   }
 }
+
+// ---- local conditioning: the cond ring ----------------------------------------------------
+// lccond[t mod NC][l][b][o] = lc[b][r(t)] · [LC_SIGNAL_l | LC_GATE_l][:, o]  (tmodel.py:155-160) for
+// the next n <= NC steps t = *step + j, r(t) = min(max(t-1, 0), n_rows-1): generation step t is
+// training position t-1, step 0 and steps past the mel take the nearest row.  Hoisted out of the
+// step kernels: inside the chain the n_lc_out x 64 product per layer would sit on the serial
+// path (arch5: 80 x 64 beside the conv's 64 x 64); here it is one launch per NC steps.
+// Block = (layer l, LCP_ROWS rows m = j·B + b); thread (o = tid & 63, row group tid >> 6): 16 rows x
+// one output column, plain f32 FMAs in k order (the lc rows staged in LDS and read as broadcasts,
+// the weight column coalesced over o and read once per 64 rows).  t and n_rows come from device words, so the launch is
+// capturable and a replayed graph follows a mel loaded later.
+constexpr int LCP_KT = 128;   // k tile staged per pass
+constexpr int LCP_ROWS = 64, LCP_RPT = LCP_ROWS / 4;   // rows per block / per thread
+
+struct LcProjK {
+  const float* lc; const float* wsig; const float* wgate; float* out;
+  const long long* step; const int* n_rows;
+  int B, L, Lo, Cd, NC, n;
+};
+
+__global__ __launch_bounds__(256) void gen_lc_proj_kernel(LcProjK a) {
+  __shared__ __attribute__((aligned(16))) float xs[LCP_ROWS][LCP_KT];
+  const int tid = threadIdx.x, l = blockIdx.x, m0 = blockIdx.y * LCP_ROWS, M = a.n * a.B;
+  const long long t0 = *a.step;
+  const int n_rows = max(*a.n_rows, 1);
+  const int o = tid & 63, oc = o & 31, rq = tid >> 6;
+  const bool ocv = oc < a.Cd;
+  const float* W = (o < 32 ? a.wsig : a.wgate) + (long)l * a.Lo * a.Cd + min(oc, a.Cd - 1);
+  float acc[LCP_RPT];
+#pragma unroll
+  for (int r = 0; r < LCP_RPT; ++r) acc[r] = 0.f;
+  for (int k0 = 0; k0 < a.Lo; k0 += LCP_KT) {
+    const int kt = min(LCP_KT, a.Lo - k0), kt4 = kt >> 2;   // Lo is a multiple of 4
+    if (k0) __syncthreads();
+    for (int e = tid; e < LCP_ROWS * kt4; e += 256) {
+      const int j = e / kt4, k = 4 * (e % kt4), m = min(m0 + j, M - 1);
+      const int b = m % a.B;
+      const long long t = t0 + m / a.B;
+      const long long r = min(max(t - 1, 0LL), (long long)n_rows - 1);
+      *(floatx4*)&xs[j][k] = *(const floatx4*)(a.lc + ((long)b * n_rows + r) * a.Lo + k0 + k);
+    }
+    __syncthreads();
+    for (int k = 0; k < kt; k += 4) {
+      float w[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[i] = W[(long)(k0 + k + i) * a.Cd];
+#pragma unroll
+      for (int r = 0; r < LCP_RPT; ++r) {
+        const floatx4 x = *(const floatx4*)&xs[LCP_RPT * rq + r][k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[r] = fmaf(x[i], w[i], acc[r]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < LCP_RPT; ++r) {
+    const int m = m0 + LCP_RPT * rq + r;
+    if (m >= M) break;
+    const int b = m % a.B, slot = (int)((t0 + m / a.B) % a.NC);
+    a.out[(((long)slot * a.L + l) * a.B + b) * 64 + o] = ocv ? acc[r] : 0.f;
+  }
+}
+
+__global__ void gen_set_word_kernel(int* dst, int v) { *dst = v; }
 
 __global__ void gen_reset_kernel(float* rings, long n_ring, unsigned long long* gran, long n_gran, int* code, int B,
                                  long long* step, int* status) {
@@ -1115,7 +1201,17 @@ struct lbwn_gen_plan {
   long long n_teacher, max_teacher;
   unsigned long long seed;
   int pre_bias;
+  // local conditioning (Lo = 0: none): the upsampled mel "lc" [B][n_rows][Lo] (dense, n_rows =
+  // the loaded mel's frames x hop <= lc_rows), the upsample stages' scratch, and the cond ring
+  // "lccond" [NC][L][B][64]; the loaded n_rows also lives in the device word at oSTEP + 12
+  int Li = 0, Lo = 0, nup = 0, up[8] = {1, 1, 1, 1, 1, 1, 1, 1}, NC = 0;
+  long long hop = 1, lc_rows = 0;
+  size_t oLC = 0, oLCACT[8] = {0, 0, 0, 0, 0, 0, 0, 0}, oLCC = 0;
+  bool up_fused = false, mel_loaded = false;
 };
+
+constexpr int G_LC_CHUNK = 64;         // default NC (steps per projection launch / persistent sub-run)
+constexpr int G_LC_CHUNK_MAX = 4096;
 
 // the per-step GEMM form: large B, shapes the split GEMM takes (N % 4, K % 4, row strides)
 static bool gemm_form_ok(const lbwn_gen_plan* p) {
@@ -1133,9 +1229,30 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   LBWN_REQUIRE(a && out && B >= 1 && max_steps >= 1 && max_teacher >= 0, "gen_plan_create: bad arguments");
   LBWN_REQUIRE(a->n_res <= 32 && a->n_dil <= 32, "gen: n_res/n_dil must be <= 32");
   LBWN_REQUIRE(a->n_blocks * a->n_block_layers <= G_MAXL, "gen: more than %d layers (tap cache)", G_MAXL);
-  LBWN_REQUIRE(a->n_lc_out == 0, "gen: local conditioning is not supported by the cached generator "
-                                 "(imodel.py has no LC path)");
   LBWN_REQUIRE(a->n_quant <= 512, "gen: n_quant must be <= 512");
+  // local conditioning: the training plan's limits (lbwn_plan_create)
+  long long hop = 1;
+  int lc_chunk = G_LC_CHUNK;
+  if (a->n_lc_out > 0) {
+    LBWN_REQUIRE(a->n_lc_upsample >= 1 && a->n_lc_upsample <= 8, "gen: LC needs 1..8 upsample stages");
+    for (int i = 0; i < a->n_lc_upsample; ++i) {
+      LBWN_REQUIRE(a->lc_upsample[i] >= 1, "gen: bad lc_upsample stride");
+      hop *= a->lc_upsample[i];
+      LBWN_REQUIRE(hop <= (1LL << 30), "gen: mel hop too large");
+    }
+    LBWN_REQUIRE(a->n_lc_in >= 4 && a->n_lc_in % 4 == 0 && a->n_lc_out % 4 == 0,
+                 "gen: n_lc_in/n_lc_out must be multiples of 4");
+    LBWN_REQUIRE((max_steps + hop - 1) / hop * hop < (1LL << 31), "gen: max_steps too large for an LC plan");
+    if (const char* ce = getenv("LBWN_GEN_LC_CHUNK")) {
+      char* end = nullptr;
+      const long v = strtol(ce, &end, 10);
+      LBWN_REQUIRE(end != ce && *end == 0 && v >= 1 && v <= G_LC_CHUNK_MAX,
+                   "gen: LBWN_GEN_LC_CHUNK must be an integer in 1..%d (got '%s')", G_LC_CHUNK_MAX, ce);
+      lc_chunk = (int)v;
+    }
+    LBWN_REQUIRE((long long)lc_chunk * B / LCP_ROWS < 65535, "gen: LBWN_GEN_LC_CHUNK %d x batch_sz %d is too large",
+                 lc_chunk, B);   // the projection's grid: one block row per LCP_ROWS (step, stream) pairs
+  }
   lbwn_gen_plan* p = new lbwn_gen_plan();
   p->a = *a;
   p->B = B;
@@ -1194,6 +1311,21 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     }
     p->oGSPL = gcarve(cur, 4 * (size_t)most);
   }
+  if (a->n_lc_out > 0) {
+    p->Li = a->n_lc_in; p->Lo = a->n_lc_out; p->nup = a->n_lc_upsample; p->hop = hop; p->NC = lc_chunk;
+    for (int i = 0; i < p->nup; ++i) p->up[i] = a->lc_upsample[i];
+    const long long frames = (max_steps + hop - 1) / hop;
+    p->lc_rows = frames * hop;
+    p->oLC = gcarve(cur, 4 * (size_t)B * p->lc_rows * p->Lo);
+    long long r = frames;
+    for (int i = 0; i + 1 < p->nup; ++i) {   // outputs of the stages before the last
+      r *= p->up[i];
+      p->oLCACT[i] = gcarve(cur, 4 * (size_t)B * r * p->Lo);
+    }
+    p->oLCACT[p->nup - 1] = p->oLC;
+    p->oLCC = gcarve(cur, 4 * (size_t)p->NC * p->L * B * 64);
+    p->up_fused = lbwn_lc_up_fused_ok(p->nup, p->up, p->Li, p->Lo) != 0;
+  }
   p->total = cur;
   *out = p;
   return 0;
@@ -1213,6 +1345,8 @@ extern "C" int lbwn_gen_tensor(const lbwn_gen_plan* p, const char* name, size_t*
   else if (!strcmp(name, "trace")) { *off = p->oTRACE; *bytes = 8 * (size_t)(2 * p->L + 8 + 128 + 2 * P_NH); }
   else if (!strcmp(name, "rings")) { *off = p->oRING; *bytes = 4 * (size_t)p->n_ring; }
   else if (!strcmp(name, "teacher")) { *off = p->oTEACH; *bytes = 4 * (size_t)std::max<long long>(1, p->n_teacher); }
+  else if (p->Lo > 0 && !strcmp(name, "lc")) { *off = p->oLC; *bytes = 4 * B * (size_t)p->lc_rows * p->Lo; }
+  else if (p->Lo > 0 && !strcmp(name, "lccond")) { *off = p->oLCC; *bytes = 4 * (size_t)p->NC * p->L * B * 64; }
   else LBWN_REQUIRE(false, "gen_tensor: unknown tensor '%s'", name);
   return 0;
 }
@@ -1230,6 +1364,7 @@ extern "C" int lbwn_gen_start(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
                "gen_start: teacher length %lld exceeds plan capacity %lld", (long long)n_teacher, p->max_teacher);
   hipStream_t st = (hipStream_t)stream;
   p->n_teacher = teacher ? n_teacher : 0;
+  p->mel_loaded = false;
   p->seed = seed;
   p->pre_bias = pre_bias;
   gen_reset_kernel<<<256, 256, 0, st>>>(gat<float>(ws, p->oRING), p->n_ring, gat<unsigned long long>(ws, p->oGRAN),
@@ -1255,10 +1390,55 @@ extern "C" int lbwn_gen_start(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
   return 0;
 }
 
+extern "C" int lbwn_gen_set_mel(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const float* mel, int64_t n_frames,
+                                void* stream) {
+  LBWN_REQUIRE(p && P && ws, "gen_set_mel: null argument");
+  LBWN_REQUIRE(p->Lo > 0, "gen_set_mel: the arch has no local conditioning");
+  LBWN_REQUIRE(mel, "gen_set_mel: mel is null");
+  LBWN_REQUIRE(n_frames >= 1, "gen_set_mel: n_frames must be >= 1");
+  LBWN_REQUIRE(n_frames <= p->lc_rows / p->hop, "gen_set_mel: %lld frames x hop %lld exceed the plan's %lld rows",
+               (long long)n_frames, p->hop, p->lc_rows);
+  LBWN_REQUIRE(P->lc_sig && P->lc_gate, "gen_set_mel: LC_SIGNAL/LC_GATE pointers are null");
+  for (int i = 0; i < p->nup; ++i) LBWN_REQUIRE(P->lc_up[i], "gen_set_mel: LC_UPSAMPLE_%d pointer is null", i);
+  hipStream_t st = (hipStream_t)stream;
+  const long long frames = (long long)p->B * n_frames;
+  LBWN_REQUIRE(frames * p->hop < (1LL << 31), "gen_set_mel: too many rows");
+  float* act[8];
+  for (int i = 0; i < p->nup; ++i) act[i] = gat<float>(ws, p->oLCACT[i]);
+  if (p->up_fused) {
+    if (int e = lbwn_lc_up_fwd_launch(p->nup, p->up, p->Li, p->Lo, (int)frames, mel, P->lc_up, act, st)) return e;
+  } else {   // per-stage GEMMs against the [s][O][I] filters read as k-contiguous (engine.cpp cond_forward)
+    const float* in = mel;
+    long long rows = frames;
+    int I = p->Li;
+    for (int i = 0; i < p->nup; ++i) {
+      const int s = p->up[i];
+      lbwn_gemm_args g;
+      memset(&g, 0, sizeof(g));
+      g.A = in; g.lda = I; g.B = P->lc_up[i]; g.ldb = I; g.C = act[i]; g.ldc = (long)s * p->Lo;
+      g.M = (int)rows; g.N = s * p->Lo; g.K = I;
+      if (int e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st)) return e;
+      in = act[i];
+      rows *= s;
+      I = p->Lo;
+    }
+  }
+  gen_set_word_kernel<<<1, 1, 0, st>>>(gat<int>(ws, p->oSTEP + 12), (int)(n_frames * p->hop));
+  LBWN_CHECK_LAUNCH();
+  p->mel_loaded = true;
+  return 0;
+}
+
 extern "C" int lbwn_gen_is_persistent(const lbwn_gen_plan* p) { return p && p->persist ? 1 : 0; }
+
+static void launch_wave(const lbwn_gen_plan* p, const WaveK& c, hipStream_t st) {
+  if (p->Lo > 0) gen_wave_kernel<true><<<p->B, 512, 0, st>>>(c);
+  else gen_wave_kernel<false><<<p->B, 512, 0, st>>>(c);
+}
 
 static WaveK wave_args(lbwn_gen_plan* p, const lbwn_params* P, void* ws) {
   WaveK c;
+  c.lccond = p->Lo > 0 ? gat<float>(ws, p->oLCC) : nullptr; c.NC = p->NC;
   c.pre = P->pre; c.pre_b = P->pre_b; c.img = gat<float>(ws, p->oGIMG);
   c.gc_proj = p->a.n_gc_embed > 0 ? gat<float>(ws, p->oGCP) : nullptr;
   c.rings = gat<float>(ws, p->oRING); c.zcat = gat<float>(ws, p->oZCAT);
@@ -1292,7 +1472,7 @@ static int gen_run_gemm(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_
   p2.N = p->Q; p2.K = p->Cp; p2.bias = P->post2_b; p2.relu_out = 0;
   d.part = LG; d.parts = 1; d.bias = nullptr;   // b2 added by the GEMM
   for (int i = 0; i < n_steps; ++i) {
-    gen_wave_kernel<<<p->B, 512, 0, st>>>(c);
+    launch_wave(p, c, st);
     LBWN_CHECK_LAUNCH();
     if (int e = lbwn_gemm_launch(sk, 1, 0, p->gsplit[0], SPL, st)) return e;
     if (int e = lbwn_gemm_launch(p1, 1, 0, p->gsplit[1], SPL, st)) return e;
@@ -1303,9 +1483,8 @@ static int gen_run_gemm(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_
   return 0;
 }
 
-extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_steps, void* stream) {
-  LBWN_REQUIRE(p && P && ws && n_steps >= 0, "gen_run: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
+// n_steps steps in the plan's form (LC plans: n_steps <= NC, their cond-ring rows projected)
+static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_steps, hipStream_t st) {
   DrawK d;
   memset(&d, 0, sizeof(d));
   d.Q = p->Q; d.B = p->B; d.bias = P->post2_b;
@@ -1330,10 +1509,12 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
     k.trace = p->trace ? gat<long long>(ws, p->oTRACE) : nullptr;
     k.Bg = p->pbg;
     k.gstep = reinterpret_cast<long long*>(g + p->n_gran_core);
-    gen_persist_kernel<<<p->pgroups * (p->pbg + P_NH), 512, 0, st>>>(k);
-    LBWN_CHECK_LAUNCH();
-    gen_decode_kernel<<<std::max(1, std::min(1024, (int)(((long long)p->B * n_steps + 255) / 256))), 256, 0, st>>>(
-        d.samples, d.wav, k.step, p->B, p->max_steps, n_steps, p->Q);
+    if (p->Lo > 0) {
+      k.lccond = gat<float>(ws, p->oLCC); k.NC = p->NC;
+      gen_persist_kernel<true><<<p->pgroups * (p->pbg + P_NH), 512, 0, st>>>(k);
+    } else {
+      gen_persist_kernel<false><<<p->pgroups * (p->pbg + P_NH), 512, 0, st>>>(k);
+    }
     LBWN_CHECK_LAUNCH();
     return 0;
   }
@@ -1345,6 +1526,7 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
   c.step = gat<long long>(ws, p->oSTEP); c.code = gat<int>(ws, p->oCODE);
   c.trace = p->trace ? gat<long long>(ws, p->oTRACE) : nullptr;
   c.B = p->B; c.L = p->L; c.nbl = p->nbl; c.Cr = p->Cr; c.Cd = p->Cd; c.pre_bias = p->pre_bias;
+  c.lccond = p->Lo > 0 ? gat<float>(ws, p->oLCC) : nullptr; c.NC = p->NC;
   // skip = z_cat·SKIPcat (+Σb and relu applied by the consumer), h = relu(relu(skip)·POST1 + b1),
   // logits = h·POST2 + b2 (summed in the sampler)
   GemvK sk = {}, p1 = {}, p2 = {};
@@ -1366,7 +1548,7 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
     sk.trace = tb; p1.trace = tb + 8; p2.trace = tb + 16;
   }
   for (int i = 0; i < n_steps; ++i) {
-    gen_wave_kernel<<<p->B, 512, 0, st>>>(c);
+    launch_wave(p, c, st);
     gen_gemv_kernel<<<gsk, 256, 0, st>>>(sk);
     gen_gemv_kernel<<<gp1, 256, 0, st>>>(p1);
     gen_gemv_kernel<<<gp2, 256, 0, st>>>(p2);
@@ -1376,3 +1558,30 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
   return 0;
 }
 
+extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_steps, void* stream) {
+  LBWN_REQUIRE(p && P && ws && n_steps >= 0, "gen_run: bad arguments");
+  LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded, "gen_run: LC plan without a mel (lbwn_gen_set_mel after lbwn_gen_start)");
+  hipStream_t st = (hipStream_t)stream;
+  if (p->Lo == 0) {
+    if (int e = gen_run_sub(p, P, ws, n_steps, st)) return e;
+  } else {
+    // sub-runs of <= NC steps: project their cond-ring rows (step t -> slot t mod NC), then the steps
+    LcProjK k;
+    k.lc = gat<float>(ws, p->oLC); k.wsig = P->lc_sig; k.wgate = P->lc_gate; k.out = gat<float>(ws, p->oLCC);
+    k.step = gat<long long>(ws, p->oSTEP); k.n_rows = gat<int>(ws, p->oSTEP + 12);
+    k.B = p->B; k.L = p->L; k.Lo = p->Lo; k.Cd = p->Cd; k.NC = p->NC;
+    for (int done = 0; done < n_steps; done += p->NC) {
+      k.n = std::min(p->NC, n_steps - done);
+      gen_lc_proj_kernel<<<dim3(p->L, (k.n * p->B + LCP_ROWS - 1) / LCP_ROWS), 256, 0, st>>>(k);
+      LBWN_CHECK_LAUNCH();
+      if (int e = gen_run_sub(p, P, ws, k.n, st)) return e;
+    }
+  }
+  if (p->persist && n_steps > 0) {   // the persistent form's wav: decode the call's samples [step - n_steps, step)
+    gen_decode_kernel<<<std::max(1, std::min(1024, (int)(((long long)p->B * n_steps + 255) / 256))), 256, 0, st>>>(
+        gat<int>(ws, p->oSAMP), gat<float>(ws, p->oWAV), gat<long long>(ws, p->oSTEP), p->B, p->max_steps, n_steps,
+        p->Q);
+    LBWN_CHECK_LAUNCH();
+  }
+  return 0;
+}

@@ -5,7 +5,8 @@ a '<prefix>.safetensors' written by this build's train.py (reference serial name
 while_loop becomes WaveNetGen's device-resident generation (hipGraph-replayed chunks);
 librosa (absent here) is replaced by scipy.io.wavfile for reading the teacher wav and
 writing 'gen.i<k>.wav' (float32).  The reference hard-codes gc_ids = [5, 6]
-(generate.py:94); --gc-ids overrides, and the list is cycled over the batch.
+(generate.py:94); --gc-ids overrides, and the list is cycled over the batch.  Archs with local
+conditioning (the reference's generator has none) take their mel from --mel-npy.
 """
 import argparse
 import json
@@ -31,6 +32,11 @@ def get_args(argv=None):
     p.add_argument('--batch-size', '-b', type=int, default=10, help='Number of .wav files to generate simultaneously')
     p.add_argument('--gc-ids', type=str, default='5,6', help='(build extension) voice ids, cycled over the batch')
     p.add_argument('--seed', type=int, default=0, help='(build extension) sampling seed')
+    p.add_argument('--mel-npy', type=str, default=None, metavar='PATH',
+                   help='(build extension) local conditioning for LC archs: a .npy of [frames, n_lc_in] '
+                        '(shared by the batch) or [batch, frames, n_lc_in].  Upsampled mel row i-1 conditions '
+                        'step i, counted from the start of the teacher (step 0 uses row 0), so it must hold '
+                        'at least (steps - 1) / hop frames for the gen_seconds + teacher seconds requested')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('ckpt', metavar='CHECKPOINT_PREFIX', type=str)
     p.add_argument('wav_dir', metavar='OUTPUT_WAV_DIR', type=str)
@@ -67,7 +73,7 @@ def main(argv=None):
     from sys import stderr
     import numpy as np
     import torch
-    from lbwn.arch import normalize_arch
+    from lbwn.arch import mel_hop_sz, normalize_arch
     from lbwn.ckpt import ckpt_file
     from lbwn.imodel import WaveNetGen
 
@@ -82,18 +88,35 @@ def main(argv=None):
     else:
         teacher_vec, teacher_seconds = None, 0
 
+    gen_sz = int((args.gen_seconds + teacher_seconds) * args.sample_rate)
+    mel = None
+    if arch['n_lc_out'] > 0:
+        if args.mel_npy is None:
+            print('ARCH_FILE has local conditioning: --mel-npy is required', file=stderr)
+            sys.exit(1)
+        if not os.access(args.mel_npy, os.R_OK):
+            print("Couldn't find mel file {}".format(args.mel_npy), file=stderr)
+            sys.exit(1)
+        mel = np.load(args.mel_npy)
+        hop = mel_hop_sz(arch)
+        if mel.ndim not in (2, 3) or gen_sz > mel.shape[-2] * hop + 1:
+            print('mel {} is too short: {} steps ({} s generated + {} s teacher) need {} frames of hop {}'.format(
+                tuple(mel.shape), gen_sz, args.gen_seconds, teacher_seconds, -(-(gen_sz - 1) // hop), hop),
+                file=stderr)
+            sys.exit(1)
+
     net = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                      arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
-                     args.batch_size, args.chunk_size, teacher_vec, seed=args.seed)
+                     args.batch_size, args.chunk_size, teacher_vec, seed=args.seed, n_lc_in=arch['n_lc_in'],
+                     n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'])
     print('Building graph.')
     print('Restoring from {}'.format(args.ckpt))
     net.restore(args.ckpt)
     print('Initializing buffers.')
     ids = [int(v) for v in args.gc_ids.split(',') if v.strip()]
     gc_ids = [ids[i % len(ids)] for i in range(args.batch_size)] if arch['n_gc_embed'] else None
-    gen_sz = int((args.gen_seconds + teacher_seconds) * args.sample_rate)
     print('Starting inference...')
-    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids)
+    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel)
     wav_streams = wav_streams.cpu().numpy()
 
     from scipy.io import wavfile

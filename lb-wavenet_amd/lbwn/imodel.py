@@ -8,6 +8,11 @@ steps and replayed.  The reference's generation path does not run as shipped (SU
 this class implements its stated intent (tests.py:1: tmodel and imodel are equivalent
 functions), adding PRE_BIAS to the input embedding by default (``pre_bias=False``
 reproduces imodel.py:75-77 literally).
+
+Local conditioning (keyword-only ``n_lc_in, n_lc_out, lc_upsample``; the reference's generator
+has no LC path): ``init_buffers`` / ``run`` take ``mel`` [B, n_frames, n_lc_in] (or [n_frames,
+n_lc_in], shared by every stream).  Generation step i is training position i-1, so it is
+conditioned on row max(i-1, 0) of the upsampled mel; n_frames·hop rows cover n_frames·hop + 1 steps.
 """
 import ctypes
 import sys
@@ -16,16 +21,19 @@ import numpy as np
 import torch
 
 from . import _lib
-from .arch import ParamLayout, normalize_arch
+from .arch import ParamLayout, mel_hop_sz, normalize_arch
 
 
 class WaveNetGen:
     def __init__(self, n_blocks, n_block_layers, n_quant, n_res, n_dil, n_skip, n_post1, n_gc_embed,
                  n_gc_category, use_bias, batch_sz, chunk_sz, teacher_vec=None, *, pre_bias=True, seed=0,
-                 device='cuda', graph=True):
+                 device='cuda', graph=True, n_lc_in=0, n_lc_out=0, lc_upsample=()):
         self.arch = normalize_arch(dict(n_blocks=n_blocks, n_block_layers=n_block_layers, n_quant=n_quant,
                                         n_res=n_res, n_dil=n_dil, n_skip=n_skip, n_post=n_post1,
-                                        n_gc_embed=n_gc_embed, n_gc_category=n_gc_category, use_bias=use_bias))
+                                        n_gc_embed=n_gc_embed, n_gc_category=n_gc_category, use_bias=use_bias,
+                                        n_lc_in=n_lc_in if n_lc_out else 0, n_lc_out=n_lc_out,
+                                        lc_upsample=list(lc_upsample) if n_lc_out else []))
+        self.hop = mel_hop_sz(self.arch) if self.arch['n_lc_out'] > 0 else 0
         self.batch_sz = batch_sz
         self.chunk_sz = chunk_sz
         self.pre_bias = bool(pre_bias)
@@ -71,6 +79,12 @@ class WaveNetGen:
         for k in ('n_blocks', 'n_block_layers', 'n_quant', 'n_res', 'n_dil', 'n_skip', 'n_post',
                   'n_gc_embed', 'n_gc_category', 'n_lc_in', 'n_lc_out'):
             setattr(a, k, int(self.arch[k]))
+        ups = self.arch['lc_upsample'] if self.arch['n_lc_out'] > 0 else []
+        if len(ups) > 8:
+            raise ValueError('lc_upsample has %d stages, at most 8 are supported' % len(ups))
+        a.n_lc_upsample = len(ups)
+        for i, s in enumerate(ups):
+            a.lc_upsample[i] = int(s)
         a.use_bias = int(self.arch['use_bias'])
         self._arch_c = a
         h = ctypes.c_void_p()
@@ -85,8 +99,9 @@ class WaveNetGen:
         base = self.flat.data_ptr()
         for field, off in self.layout.kind_base.items():
             if field.startswith('lc_up'):
-                continue
-            setattr(P, field, base + 4 * off)
+                P.lc_up[int(field[5:])] = base + 4 * off
+            else:
+                setattr(P, field, base + 4 * off)
         self._params_c = P
         self._graph = None
         return self
@@ -102,8 +117,36 @@ class WaveNetGen:
         _lib.check(self.lib.lbwn_gen_tensor(self._plan, name.encode(), ctypes.byref(off), ctypes.byref(nb)))
         return self._ws[off.value:off.value + nb.value].view(dtype)
 
-    def init_buffers(self, gc_ids=None):
-        """imodel.init_buffers: zero the lookback/loop buffers, load teacher + GC ids."""
+    def _check_mel(self, mel, gen_sz=None):
+        """mel as a float32 [B, n_frames, n_lc_in] array/tensor (None for archs without LC);
+        ValueError on a missing mel, a shape mismatch or a mel too short for gen_sz steps."""
+        if self.arch['n_lc_out'] == 0:
+            if mel is not None:
+                raise ValueError('mel given, but the arch has no local conditioning')
+            return None
+        if mel is None:
+            raise ValueError('LC arch: mel [batch_sz, n_frames, n_lc_in] required')
+        if not isinstance(mel, torch.Tensor):
+            mel = np.asarray(mel, np.float32)
+        Li = self.arch['n_lc_in']
+        shp = tuple(mel.shape)
+        if len(shp) == 2:
+            shp = (self.batch_sz,) + shp
+            mel = mel[None].expand(*shp) if isinstance(mel, torch.Tensor) else np.broadcast_to(mel[None], shp)
+        if len(shp) != 3 or shp[0] != self.batch_sz or shp[2] != Li or shp[1] < 1:
+            raise ValueError('mel has shape %s, expected [%d, n_frames, %d] or [n_frames, %d]'
+                             % (tuple(mel.shape), self.batch_sz, Li, Li))
+        if gen_sz is not None and gen_sz > shp[1] * self.hop + 1:
+            raise ValueError('gen_sz %d needs more than the %d mel frames given (%d rows cover %d steps)'
+                             % (gen_sz, shp[1], shp[1] * self.hop, shp[1] * self.hop + 1))
+        return mel
+
+    def init_buffers(self, gc_ids=None, mel=None):
+        """imodel.init_buffers: zero the lookback/loop buffers, load teacher + GC ids (+ the mel of
+        an LC arch, upsampled once)."""
+        mel = self._check_mel(mel)
+        if mel is not None:   # frames past the plan's ceil(max_steps / hop) condition no step
+            mel = mel[:, :-(-self.max_steps // self.hop)]
         self._gc = None
         if self.arch['n_gc_embed'] > 0:
             if gc_ids is None:
@@ -116,6 +159,12 @@ class WaveNetGen:
         _lib.check(self.lib.lbwn_gen_start(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                            _lib.ptr(self._gc), _lib.ptr(t), 0 if t is None else t.numel(),
                                            self.seed, int(self.pre_bias), _lib.stream_ptr()))
+        if mel is not None:
+            if not isinstance(mel, torch.Tensor):
+                mel = torch.from_numpy(np.ascontiguousarray(mel, np.float32))
+            self._mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
+            _lib.check(self.lib.lbwn_gen_set_mel(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
+                                                 self._mel.data_ptr(), self._mel.shape[1], _lib.stream_ptr()))
 
     def _launch(self, n):
         _lib.check(self.lib.lbwn_gen_run(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(), n,
@@ -143,12 +192,14 @@ class WaveNetGen:
         if n_steps - done > 0:
             self._launch(n_steps - done)
 
-    def run(self, gen_sz, gc_ids=None):
+    def run(self, gen_sz, gc_ids=None, mel=None):
         """The reference's sess.run(wave_ops) (generate.py:110): generate gen_sz steps from a
-        fresh state; the returned waveform holds whole chunks only (imodel.py:256-258)."""
+        fresh state; the returned waveform holds whole chunks only (imodel.py:256-258).  LC archs:
+        mel must cover the run, gen_sz <= n_frames·hop + 1."""
+        mel = self._check_mel(mel, int(gen_sz))
         if self._plan is None or self.max_steps < gen_sz:
             self.build_graph(gen_sz)
-        self.init_buffers(gc_ids)
+        self.init_buffers(gc_ids, mel)
         self.step(int(gen_sz))
         self.check_status()
         n_out = (int(gen_sz) // self.chunk_sz) * self.chunk_sz
