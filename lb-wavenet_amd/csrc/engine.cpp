@@ -25,6 +25,14 @@ struct lbwn_plan {
   size_t oMBS = 0, oMBR = 0;
   bool mb_s = false, mb_r = false;
   bool mbits_ok = true;
+  // Masked-position skip (bf16-split path): the fused prologue writes the live lists of the step's
+  // ids (prologue.h live_lists_body: tlive [ceil(M/256)] | klive [ceil(M/32)] | nklive | kpre
+  // [ceil(M/32) + 1], ints at oLIVE); the backward's dH1 / dS / dZ skip dead row tiles and dPOST2 /
+  // dPOST1 / dSKIP skip dead k-steps inside their split-K slices: the same values bit for bit.
+  // LBWN_SKIP_MASKED=0 at plan creation turns it off (the A/B switch).
+  size_t oLIVE = 0;
+  bool skip_ok = true;
+  bool live_valid = false;   // the last forward wrote the lists
   bool dv_blk = false;     // the last backward exported DV k-blocked ([2L][m32(M)][32])
   int head_colparts = 0;   // post2-bias column partial rows the last forward's head wrote (0: none)
   lbwn_arch a;
@@ -376,6 +384,8 @@ int lbwn_plan_create(const lbwn_arch* a, int B, int T, lbwn_plan** out) {
     // layer_wgrad_kernel over the chain's exports (1; 16-position backward on 128-position tiles)
     const char* mv = getenv("LBWN_GEMM_MBITS");
     p->mbits_ok = !(mv && mv[0] == '0');
+    const char* sv = getenv("LBWN_SKIP_MASKED");
+    p->skip_ok = !(sv && sv[0] == '0');
     const char* wv = getenv("LBWN_BWD_WGRAD");
     p->wg_out = (wv && wv[0] == '1') && bwd_nw == 8;
     const char* cv = getenv("LBWN_COLSUM_SIDE");
@@ -509,6 +519,7 @@ int lbwn_plan_create(const lbwn_arch* a, int B, int T, lbwn_plan** out) {
     p->oLCX = carve(cur, 2 * (size_t)L * std::max(lbwn_lc_image_x3_elems(), lbwn_lc_image16_elems()));
   p->oMBS = carve(cur, 8 * (size_t)lbwn_gemm_mbits_words(M, p->Cs));
   p->oMBR = carve(cur, 8 * (size_t)lbwn_gemm_mbits_words(M, p->Cp));
+  p->oLIVE = carve(cur, sizeof(int) * (size_t)((M + 255) / 256 + 2 * ((M + 31) / 32) + 2));
   p->oHEADP = carve(cur, sizeof(float) * 3 * 2048);
   p->oBSUM = carve(cur, sizeof(float) * (size_t)p->Cs);
   p->oWPK = carve(cur, sizeof(float) * (size_t)L * lbwn_layer_image_floats());
@@ -539,6 +550,12 @@ int lbwn_plan_tensor(const lbwn_plan* p, const char* name, size_t* off, size_t* 
   else if (!strcmp(name, "dh")) { *off = p->oDH; *bytes = f * M * p->Cp; }
   else if (!strcmp(name, "ds")) { *off = p->oDS; *bytes = f * M * p->Cs; }
   else if (!strcmp(name, "dz")) { *off = p->oDZ; *bytes = f * M * p->L * p->Cd; }
+  // the masked-position live lists (int32), valid after a forward that wrote them (bf16-split chain
+  // plans without LBWN_SKIP_MASKED=0): klive's first nklive[0] entries
+  else if (!strcmp(name, "tlive")) { *off = p->oLIVE; *bytes = 4 * ((M + 255) / 256); }
+  else if (!strcmp(name, "klive")) { *off = p->oLIVE + 4 * ((M + 255) / 256); *bytes = 4 * ((M + 31) / 32); }
+  else if (!strcmp(name, "nklive")) { *off = p->oLIVE + 4 * ((M + 255) / 256 + (M + 31) / 32); *bytes = 4; }
+  else if (!strcmp(name, "kpre")) { *off = p->oLIVE + 4 * ((M + 255) / 256 + (M + 31) / 32 + 1); *bytes = 4 * ((M + 31) / 32 + 1); }
   else if (!strcmp(name, "cond") && p->Lo) { *off = p->oCOND; *bytes = f * M * 2 * p->L * p->Cd; }
   else if (!strcmp(name, "dvall") && p->Lo) {   // rows [M][L·2Cd], or k-blocked [2L][m32(M)][32] (dv_blk)
     *off = p->oDVALL;
@@ -550,6 +567,12 @@ int lbwn_plan_tensor(const lbwn_plan* p, const char* name, size_t* off, size_t* 
   return 0;
 }
 size_t lbwn_plan_workspace_bytes(const lbwn_plan* p) { return p ? p->total : 0; }
+
+// the masked-position live lists (lbwn_plan::oLIVE)
+static int* live_t(const lbwn_plan* p, void* ws) { return reinterpret_cast<int*>(static_cast<char*>(ws) + p->oLIVE); }
+static int* live_k(const lbwn_plan* p, void* ws) { return live_t(p, ws) + (p->M + 255) / 256; }
+static int* live_n(const lbwn_plan* p, void* ws) { return live_k(p, ws) + (p->M + 31) / 32; }
+static int* live_p(const lbwn_plan* p, void* ws) { return live_n(p, ws) + 1; }
 
 // pre-split planes of weight i when the bf16-split GEMM is active, else null
 static const unsigned short* w3(const lbwn_plan* p, void* ws, int i) {
@@ -834,6 +857,7 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
   // zeroed here, read by the host after the step (lbwn_plan_tensor "status")
   // (in the fused prologue below when the bf16-split chains run)
   const bool fused_pro = lbwn_gemm_mode() == 1 && p->chain;
+  p->live_valid = fused_pro && p->skip_ok;
   if (!fused_pro && (e = lbwn_zero_launch(at<char>(ws, p->oSTATUS), 16 + 2 * p->nflag_bytes, st))) return e;
   p->bwd_flags_fresh = true;
   // the fused LC upsample depends only on the mel input and the upsample filters: it runs on
@@ -895,6 +919,10 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
     pa.q = wav_q; pa.pre = P->pre; pa.pre_b = P->pre_b; pa.X = X; pa.xls = p->x_layer_stride; pa.save = save;
     pa.nbl = p->nbl; pa.B = B; pa.T = T; pa.H = H; pa.Q = p->Q;
     pa.zero = at<char>(ws, p->oSTATUS); pa.zero_bytes = 16 + 2 * p->nflag_bytes;
+    if (p->skip_ok) {
+      pa.ids = ids; pa.tlive = live_t(p, ws); pa.klive = live_k(p, ws); pa.nklive = live_n(p, ws);
+      pa.kpre = live_p(p, ws);
+    }
     if ((e = lbwn_step_prologue_launch(pa, st))) return e;
   } else {
     if (x3 && p->chain &&
@@ -1049,6 +1077,20 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   float* CPART = at<float>(ws, p->oCPART);
   const bool fcols = lbwn_gemm_mode() == 1;
   if (fcols && G->post1_b) g.colpart = CPART;
+  // masked-position skip: the forward on this plan wrote the lists, and only the launch forms
+  // that take them
+  const bool live = p->live_valid && lbwn_gemm_mode() == 1;
+  auto row_live = [&](const lbwn_gemm_args& a) {
+    return live && lbwn_gemm_row_live_form(a.M, a.N, a.K, 1, a.b3 != nullptr, a.row_exact, a.colpart != nullptr)
+               ? live_t(p, ws) : nullptr;
+  };
+  auto k_live = [&](lbwn_gemm_args& a) {   // K = the positions
+    if (!live || a.K != (int)M || !lbwn_gemm_k_live_form(a.M, a.N, a.K)) return;
+    a.k_live = live_k(p, ws);
+    a.nk_live = live_n(p, ws);
+    a.k_pre = live_p(p, ws);
+  };
+  g.row_live = row_live(g);
   Probe(p, st, "dh");
   if ((e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st))) return e;
   Probe::end(p, st, "dh");
@@ -1060,6 +1102,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   g.row_exact = 1;
   if (p->mb_s) g.mbits = at<unsigned long long>(ws, p->oMBS);   // (S > 0) from the skip GEMM's epilogue
   if (fcols && G->skip_b) g.colpart = CPART + (long)lbwn_colpart_parts(M) * Cp;
+  g.row_live = row_live(g);
   Probe(p, st, "ds");
   if ((e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st))) return e;
   Probe::end(p, st, "ds");
@@ -1071,6 +1114,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   g.b3 = w3(p, ws, W3_SKIP_B);
   if (dz_chain) g.c_chain_ls = m32(M) * 32;
   g.xcd2d = p->dz_xcd2d;
+  g.row_live = row_live(g);
   Probe(p, st, "dz");
   if ((e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st))) return e;
   Probe::end(p, st, "dz");
@@ -1127,6 +1171,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     lbwn_gemm_args gk = gemm0();
     gk.A = Z; gk.lda = ldz; gk.B = DS; gk.ldb = Cs; gk.C = G->skip; gk.ldc = Cs; gk.M = (int)ldz; gk.N = Cs;
     gk.K = (int)M;
+    k_live(gk);
     Probe(p, s2, "dskip");
     if ((e2 = lbwn_gemm_launch(gk, 0, 0, p->split_skip, spl, s2))) return e2;
     Probe::end(p, s2, "dskip");
@@ -1137,6 +1182,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     // dPOST2 = R2ᵀ·dlogits (db2 = Σ dlogits: the column sums above)
     lbwn_gemm_args gk = gemm0();
     gk.A = R2; gk.lda = Cp; gk.B = LOG; gk.ldb = Q; gk.C = G->post2; gk.ldc = Q; gk.M = Cp; gk.N = Q; gk.K = (int)M;
+    k_live(gk);
     Probe(p, ws_st, "dpost2");
     if ((e2 = lbwn_gemm_launch(gk, 0, 0, p->split_post2, WSPL, ws_st))) return e2;
     Probe::end(p, ws_st, "dpost2");
@@ -1144,6 +1190,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     gk = gemm0();
     gk.A = S; gk.lda = Cs; gk.relu_a = 1; gk.B = DH; gk.ldb = Cp; gk.C = G->post1; gk.ldc = Cp; gk.M = Cs;
     gk.N = Cp; gk.K = (int)M;
+    k_live(gk);
     Probe(p, ws_st, "dpost1");
     if ((e2 = lbwn_gemm_launch(gk, 0, 0, p->split_post1, WSPL, ws_st))) return e2;
     Probe::end(p, ws_st, "dpost1");

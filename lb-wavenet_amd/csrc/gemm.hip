@@ -98,6 +98,22 @@ LBWN_DEV int xcd_remap(int bid, int nwg) {
 LBWN_DEV int gemm_work() { return xcd_remap(blockIdx.x + gridDim.x * blockIdx.z, gridDim.x * gridDim.z); }
 LBWN_DEV int gemm_tile() { return gemm_work() % gridDim.x; }
 LBWN_DEV int gemm_split() { return gemm_work() / gridDim.x; }
+// k_live forms: this block's split slice of the live k-step list, entries [first, first + n): the
+// entries inside the slice's own k range [s·k_per_split, (s+1)·k_per_split), found from the prefix
+// counts k_pre.  The slices are the plain form's, so every partial sums the same non-zero terms in
+// the same order and the product is bit for bit the plain form's.  (Slices balanced over the live
+// k-steps ran dSKIP / dPOST1 20 % faster on a quarter-masked slice, but they re-associate the f32
+// sums: over the benchmark's 28 Adam steps that rounding grew to 3 % of the gradients' scale.)
+// The lists are read through the constant address space: a wave-uniform scalar load (an earlier
+// launch wrote them).  As a plain global load the index came through a VGPR, and its wait
+// (vmcnt(0)) drained the operand loads the pipeline keeps two k-steps in flight.
+LBWN_DEV int live_ld(const int* p) { return *(const __attribute__((address_space(4))) int*)p; }
+struct LiveSlice { int first, n; };
+LBWN_DEV LiveSlice live_slice(const lbwn_gemm_args& g) {
+  const int nkt = g.K / 32, q = g.k_per_split / 32, s = gemm_split();
+  const int first = live_ld(g.k_pre + min(s * q, nkt));
+  return {first, live_ld(g.k_pre + min((s + 1) * q, nkt)) - first};
+}
 // 2-D blocking of a tm × tn tile grid over the 8 XCDs (no split-K): XCD x (= block % 8 under
 // round-robin dispatch; placement is speed only) takes column half x & 1 and row quarter x >> 1,
 // row-panel-major, so its L2 holds one half of the pre-split B (dZ: 2.45 of 4.9 MB) for the whole
@@ -485,8 +501,13 @@ LBWN_DEV void x3_epilogue(const lbwn_gemm_args& g, floatx16 (&acc)[2][2], int m0
 // STAGES = 2: two LDS slots, one barrier per k-step; the next k-step's registers are split
 // into the other slot between this step's two MFMA chunks, and the loads of the step after it
 // are issued right behind (one k-step of load lead).
-template <bool A_KC, bool B_KC, bool KFULL, bool BPRE, int WM, int STAGES>
+// KL (lbwn_gemm_args::k_live; the one-slot form with both operands staged whole k-steps, K % 32
+// == 0): split slice s walks the list entries inside its own k range (live_slice: the plain
+// form's slices, so the same sums bit for bit); the operands' row pointers stand at k = 0 and every
+// k-step offset is the list entry (a wave-uniform scalar load, fetched one k-step ahead of its use).
+template <bool A_KC, bool B_KC, bool KFULL, bool BPRE, int WM, int STAGES, bool KL = false>
 __global__ __launch_bounds__(128 * WM, (WM == 2 && STAGES == 1) ? X3_OCC : 1) void gemm_x3_kernel(lbwn_gemm_args g) {
+  static_assert(!KL || (KFULL && !BPRE && STAGES == 1), "k_live: whole k-steps, one slot");
   constexpr int NTHR = 128 * WM, BM = 64 * WM, BN = 128, MI = 2, NI = 2;
   constexpr int SLOT = (BM + BN) * X3_ROW;
   __shared__ __attribute__((aligned(16))) unsigned short smem[STAGES * SLOT];
@@ -500,9 +521,11 @@ __global__ __launch_bounds__(128 * WM, (WM == 2 && STAGES == 1) ? X3_OCC : 1) vo
     __hip_atomic_fetch_add(g.step_advance, 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int t = gemm_tile();
   const int m0 = (t / tiles_n) * BM, n0 = (t % tiles_n) * BN;
-  const int kz0 = gemm_split() * g.k_per_split;
+  const int kz0 = KL ? 0 : gemm_split() * g.k_per_split;
   const int kz1 = min(g.K, kz0 + g.k_per_split);
-  const int ntiles = (kz1 - kz0 + X3_BK - 1) / X3_BK;
+  const LiveSlice ls = KL ? live_slice(g) : LiveSlice{0, 0};
+  const int ntiles = KL ? ls.n : (kz1 - kz0 + X3_BK - 1) / X3_BK;
+  const int* kl = g.k_live + ls.first;   // (KL only)
 
   floatx16 acc[MI][NI];
 #pragma unroll
@@ -520,8 +543,9 @@ __global__ __launch_bounds__(128 * WM, (WM == 2 && STAGES == 1) ? X3_OCC : 1) vo
   else sb.init(g.B, g.ldb, n0, g.N, kz0, tid, B_KC ? 0 : g.b_gstride);
   const bool relu_a = g.relu_a;
   if (ntiles > 0) {
-    sa.load(0, kz1);
-    if (BPRE) sp.load(0); else sb.load(0, kz1);
+    const int k0 = KL ? live_ld(kl) : 0;
+    sa.load(k0, kz1);
+    if (BPRE) sp.load(k0); else sb.load(k0, kz1);
     sa.store(sA, tid, relu_a);
     if (BPRE) sp.store(sB); else sb.store(sB, tid, false);
   }
@@ -568,8 +592,11 @@ __global__ __launch_bounds__(128 * WM, (WM == 2 && STAGES == 1) ? X3_OCC : 1) vo
   };
 
   if (STAGES == 1) {
+    const int lastl = max(ntiles - 1, 0);
+    int kn = (KL && ntiles > 0) ? live_ld(kl + min(1, lastl)) : 0;   // the list entry of k-step kt + 1
     for (int kt = 0; kt < ntiles; ++kt) {
-      if (kt + 1 < ntiles && X3_EXP != 4) stage_load(kt + 1);
+      if (kt + 1 < ntiles && X3_EXP != 4) stage_load(KL ? kn : kt + 1);
+      if (KL) kn = live_ld(kl + min(kt + 2, lastl));
       chunk(smem, 0);
       chunk(smem, 1);
       if (kt + 1 < ntiles) {
@@ -821,8 +848,14 @@ LBWN_DEV float quad_xor(float v) {
 // consecutive rows i, the same bytes as the k-contiguous form's two 32-B runs -- and splits them in
 // registers as above (A never passes through the LDS); B is staged like the LDS-staged kernel's
 // mn-contiguous operand (4(k) x 4(n) blocks transposed in registers, split, written as planes).
-template <int NB, bool AMN = false>   // 16-column blocks: 8 (128 columns), 10 (160: dZ's N = 1600) or 6 (96: N <= 96, arch5's dlc)
+// Masked-position skip: the k-contiguous forms take lbwn_gemm_args::row_live (a dead 256-row tile
+// runs zero k-steps: block-uniform, decided before any operand load, and the ordinary epilogue
+// writes what zero accumulators give); KL: the AMN form over lbwn_gemm_args::k_live (live_slice;
+// the pipeline is the same, the k-step index of every load is the list entry, fetched to a scalar
+// one k-step before the loads that use it).
+template <int NB, bool AMN = false, bool KL = false>   // 16-column blocks: 8 (128 columns), 10 (160: dZ's N = 1600) or 6 (96: N <= 96, arch5's dlc)
 __global__ __launch_bounds__(512, 1) void gemm_x3q_kernel(lbwn_gemm_args g) {
+  static_assert(!KL || AMN, "k_live: the weight-gradient form");
   // the k-step's column blocks run in NP parts of NH (B fragments live for one part: NB = 10 in
   // two parts of 5 spilled 32 VGPRs)
   constexpr int NP = NB == 10 ? 5 : 2;
@@ -843,10 +876,15 @@ __global__ __launch_bounds__(512, 1) void gemm_x3q_kernel(lbwn_gemm_args g) {
   constexpr bool MB = NB == 8 && !AMN;
   const bool bits_in = MB && g.split_stride == 0 && g.mbits, bits_out = MB && g.split_stride == 0 && g.mbits_out;
   const unsigned long long mbr = bits_in ? g.mbits[mw] : 0ull;
-  const int kz0 = gemm_split() * g.k_per_split;
+  const int kz0 = KL ? 0 : gemm_split() * g.k_per_split;
   const int kz1 = min(g.K, kz0 + g.k_per_split);
-  const int ntiles = (kz1 - kz0) / X3_BK;   // K % 32 == 0 (pre-split B; AMN: checked by the launcher)
+  const LiveSlice ls = KL ? live_slice(g) : LiveSlice{0, 0};
+  const int* kl = g.k_live + ls.first;   // (KL only)
+  const bool dead = !AMN && g.row_live && live_ld(g.row_live + (m0 >> 8)) == 0;
+  // K % 32 == 0 (pre-split B; AMN: checked by the launcher)
+  const int ntiles = KL ? ls.n : (dead ? 0 : (kz1 - kz0) / X3_BK);
   const int last = max(ntiles - 1, 0);
+  auto kidx = [&](int i) { return KL ? live_ld(kl + i) : i; };   // the k-step (from kz0) of the slice's step i
 
   floatx4 acc[2][NB];
 #pragma unroll
@@ -915,13 +953,16 @@ __global__ __launch_bounds__(512, 1) void gemm_x3q_kernel(lbwn_gemm_args g) {
   };
   if (AMN) sm_b.init(g.B, g.ldb, n0, g.N, kz0, tid);
   else sp.init(g.b3, g.K / X3_BK, n0, g.N, kz0, tid);
+  int kn = 0;   // KL: the list entry of the k-step the next step() loads (kt + 3)
   if (ntiles > 0) {
-    b_load(std::integral_constant<int, 0>(), 0);
+    const int k0 = kidx(0), k1 = kidx(min(1, last)), k2 = kidx(min(2, last));
+    if (KL) kn = kidx(min(3, last));
+    b_load(std::integral_constant<int, 0>(), k0);
     b_store(std::integral_constant<int, 0>(), smem);
-    a_load(std::integral_constant<int, 0>(), 0);
-    a_load(std::integral_constant<int, 1>(), min(1, last));
-    b_load(std::integral_constant<int, 1>(), min(1, last));
-    b_load(std::integral_constant<int, 0>(), min(2, last));
+    a_load(std::integral_constant<int, 0>(), k0);
+    a_load(std::integral_constant<int, 1>(), k1);
+    b_load(std::integral_constant<int, 1>(), k1);
+    b_load(std::integral_constant<int, 0>(), k2);
   }
   __syncthreads();
   const int fb_off = fr * X3Q_ROW + 8 * fq;
@@ -955,9 +996,11 @@ __global__ __launch_bounds__(512, 1) void gemm_x3q_kernel(lbwn_gemm_args g) {
     mfmas(fa, fb, 0);
     a_split(std::integral_constant<int, S>(), 0, fn[0]);
     a_split(std::integral_constant<int, S>(), 1, fn[1]);
-    a_load(std::integral_constant<int, S>(), min(kt + 3, last));
+    const int k3 = KL ? kn : min(kt + 3, last);
+    a_load(std::integral_constant<int, S>(), k3);
     b_store(std::integral_constant<int, S>(), nxt);
-    b_load(std::integral_constant<int, S>(), min(kt + 3, last));
+    b_load(std::integral_constant<int, S>(), k3);
+    if (KL) kn = live_ld(kl + min(kt + 4, last));
 #pragma unroll
     for (int part = 1; part < NP; ++part) {
       b_frags(cur, part, fb);
@@ -972,7 +1015,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3q_kernel(lbwn_gemm_args g) {
   if (ntiles > 0) {
     a_split(std::integral_constant<int, 0>(), 0, fa[0]);
     a_split(std::integral_constant<int, 0>(), 1, fa[1]);
-    a_load(std::integral_constant<int, 0>(), min(2, last));
+    a_load(std::integral_constant<int, 0>(), kidx(min(2, last)));
   }
   int kt = 0;
   for (; kt + 1 < ntiles; kt += 2) {
@@ -1223,6 +1266,13 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
                    (lbwn_gemm_x3q8_form(a.M, a.N, a.K, a_kcontig, a.b3 != nullptr, a.row_exact, a.colpart != nullptr) &&
                     split_k <= 1),
                "gemm (bf16 split): mask bits need the gemm_x3q_kernel<8> form without split-K");
+  LBWN_REQUIRE(!a.row_live || (lbwn_gemm_row_live_form(a.M, a.N, a.K, a_kcontig, a.b3 != nullptr, a.row_exact,
+                                                       a.colpart != nullptr) && split_k <= 1),
+               "gemm (bf16 split): row_live needs the k-contiguous gemm_x3q_kernel<8 / 10> form without split-K");
+  const bool klist = a.k_live || a.nk_live || a.k_pre;
+  LBWN_REQUIRE(!klist || (a.k_live && a.nk_live && a.k_pre && !a_kcontig && !b_kcontig && !a.b3 && !a.a_gstride && !a.b_gstride &&
+                          !a.colpart && !a.c_chain_ls && lbwn_gemm_k_live_form(a.M, a.N, a.K)),
+               "gemm (bf16 split): k_live needs a plain mn-contiguous weight-gradient product with K %% 32 == 0");
   // 256-row tiles (8 waves, 2-stage pipeline) for the tall k-contiguous products with N <= 2048
   // (skip fwd, post1/post2 fwd, dH1, dS: 3-8 % faster; dZ, N = 1600: step -0.5 % in a same-box
   // A/B since the epilogue and split changes); 128-row tiles at 2 blocks per CU for the rest
@@ -1242,6 +1292,7 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
     // N <= 96 (dLCcat as DVᵀ·lc, N = n_lc_out): 96-column tiles
     if ((e = gemm_setup(a, a_kcontig, b_kcontig, split_k, slab_ws, X3_BK, 256, a.N <= 96 ? 96 : 128, g, grid))) return e;
     if (a.N <= 96) gemm_x3q_kernel<6, true><<<grid, 512, 0, st>>>(g);
+    else if (klist) gemm_x3q_kernel<8, true, true><<<grid, 512, 0, st>>>(g);
     else gemm_x3q_kernel<8, true><<<grid, 512, 0, st>>>(g);
     LBWN_CHECK_LAUNCH();
     return splitk_finish(a, split_k, slab_ws, st);
@@ -1272,6 +1323,9 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
     if (kfull && pre) e = gemm_launch_x3_t<true, true, 4>(g, grid, a_kcontig, b_kcontig, st);
     else if (kfull) e = gemm_launch_x3_t<true, false, 4>(g, grid, a_kcontig, b_kcontig, st);
     else e = gemm_launch_x3_t<false, false, 4>(g, grid, a_kcontig, b_kcontig, st);
+  } else if (klist) {   // (lbwn_gemm_k_live_form: both operands mn-contiguous, K % 32 == 0, no pre-split)
+    gemm_x3_kernel<false, false, true, false, 2, 1, true><<<grid, 256, 0, st>>>(g);
+    LBWN_CHECK_LAUNCH();
   } else {
     if (kfull && pre) e = gemm_launch_x3_t<true, true, 2>(g, grid, a_kcontig, b_kcontig, st);
     else if (kfull) e = gemm_launch_x3_t<true, false, 2>(g, grid, a_kcontig, b_kcontig, st);
@@ -1318,10 +1372,24 @@ bool lbwn_gemm_x3q8_form(int M, int N, int K, int a_kcontig, int presplit, int r
          K % X3_BK == 0 && !(N <= 96) && !(N % 160 == 0 && N > 512);
 }
 
+// the k-contiguous 256-row gemm_x3q_kernel<8 / 10> launch (gemm_launch_x3's dispatch)
+bool lbwn_gemm_row_live_form(int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart) {
+  const bool wm4 = colpart || (a_kcontig && N <= 2048 && (M >= 8192 || row_exact));
+  return X3Q && X3R && lbwn_gemm_mode() == 1 && M >= 4 && N >= 4 && K >= 4 && wm4 && presplit && a_kcontig &&
+         K % X3_BK == 0 && N > 96;
+}
+// a plain product with both operands mn-contiguous: gemm_x3q_kernel<8, true> (>= 8 tiles) or the
+// 128-row gemm_x3_kernel; not the 96-column AMN form
+bool lbwn_gemm_k_live_form(int M, int N, int K) {
+  const bool amn = X3Q && M >= 256 && ((M + 255) / 256) * ((N + 127) / 128) >= 8;
+  return lbwn_gemm_mode() == 1 && M >= 4 && N >= 4 && K >= 4 && K % X3_BK == 0 && N % 4 == 0 && !(amn && N <= 96);
+}
+
 int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
                      hipStream_t st) {
   if (lbwn_gemm_mode() == 1 && a.a_codes == nullptr && a.K >= 4 && a.M >= 4 && a.N >= 4)
     return gemm_launch_x3(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
+  LBWN_REQUIRE(!a.row_live && !a.k_live && !a.nk_live && !a.k_pre, "gemm: row_live / k_live need the bf16-split form");
   LBWN_REQUIRE(a.colpart == nullptr && a.step_advance == nullptr && !a.c_chain_ls,
                "gemm: column partials / the step counter / chain-order C need the bf16-split form");
   return gemm_launch_t<16, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
@@ -1331,6 +1399,7 @@ int lbwn_gemm_launch_lean(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig,
                           hipStream_t st) {
   if (lbwn_gemm_mode() == 1 && a.a_codes == nullptr && a.K >= 4 && a.M >= 4 && a.N >= 4)
     return gemm_launch_x3(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
+  LBWN_REQUIRE(!a.row_live && !a.k_live && !a.nk_live && !a.k_pre, "gemm: row_live / k_live need the bf16-split form");
   LBWN_REQUIRE(a.colpart == nullptr, "gemm: column partials need the bf16-split form");
   return gemm_launch_t<8, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
 }

@@ -47,7 +47,23 @@ struct lbwn_gemm_args {
   // replaces mask.  lbwn_gemm_mbits_words(M, N) words each.
   unsigned long long* mbits_out;
   const unsigned long long* mbits;
+  // Masked-position skip (live_lists_body, prologue.h), both nullable.  row_live (the tall
+  // k-contiguous gemm_x3q_kernel<8 / 10> forms only, lbwn_gemm_row_live_form): [ceil(M/256)], 0 =
+  // every A row of the 256-row tile is exactly zero: the tile runs no k-step and its epilogue writes
+  // what zero accumulators give.  k_live / nk_live (the mn-contiguous weight-gradient forms only,
+  // lbwn_gemm_k_live_form): the ascending list of the 32-deep k-steps whose B rows are not all
+  // exactly zero, its length, and k_pre[k] = the number of list entries below k-step k
+  // ([K/32 + 1]).  Every split-K slice keeps its own k range and walks the list entries inside it,
+  // so each partial sums the same non-zero terms in the same order as without the list: the
+  // result is the same bit for bit (a skipped term is an exact zero).
+  const int* row_live;
+  const int* k_live;
+  const int* nk_live;
+  const int* k_pre;
 };
+// the launches that take row_live / k_live (anything else refuses them)
+bool lbwn_gemm_row_live_form(int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart);
+bool lbwn_gemm_k_live_form(int M, int N, int K);
 // the tall pre-split product that runs gemm_x3q_kernel<8> (the form mbits / mbits_out need)
 bool lbwn_gemm_x3q8_form(int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart);
 inline long lbwn_gemm_mbits_words(long M, long N) { return ((M + 255) / 256) * ((N + 127) / 128) * 8 * 64; }
@@ -135,6 +151,9 @@ struct lbwn_prologue_args {
   int nbl, B, T, H, Q;
   void* zero;
   size_t zero_bytes;
+  // nullable: the masked-position live lists of this step's ids ([B][T]; live_lists_body)
+  const int* ids;
+  int *tlive, *klive, *nklive, *kpre;
 };
 int lbwn_step_prologue_launch(const lbwn_prologue_args& a, hipStream_t st);
 int lbwn_pack_layers_fb_x3_launch(const float* sig, const float* gate, const float* sig_b, const float* gate_b,

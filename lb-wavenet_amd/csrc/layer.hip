@@ -1961,11 +1961,17 @@ struct PrologueK {
   lbwn_prologue_args a;
   SplitJobs jb;
   int nz, ns, ne, nd, np;   // blocks: zero, split (per job), embed, D-sep (all layers), pack
+  int nl;                   // 1: block 0 forms the masked-position live lists (one block, the longest)
   bool ev4, dv4;            // float4 items: embed, D-sep
 };
 __global__ __launch_bounds__(256) void step_prologue_kernel(PrologueK k) {
   const lbwn_prologue_args& a = k.a;
   long b = blockIdx.x;
+  if (b < k.nl) {
+    live_lists_body(a.ids, a.B, a.T, a.tlive, a.klive, a.nklive, a.kpre);
+    return;
+  }
+  b -= k.nl;
   if (b < (long)k.ns * a.njobs) {
     split_planes_body(k.jb, (int)(b / k.ns), b % k.ns, k.ns);
     return;
@@ -3450,7 +3456,9 @@ int lbwn_step_prologue_launch(const lbwn_prologue_args& a, hipStream_t st) {
   k.nd = blocks((long)dsep_rows(a.L, a.nbl, a.B) * (k.dv4 ? a.Cr / 4 : a.Cr), 256, 2048);
   k.nz = a.zero_bytes ? blocks((long)(a.zero_bytes / 4), 1024, 256) : 0;
   k.np = 2 * a.L + (a.lcout ? a.L : 0) + ((a.skip_b && a.bsum) ? (a.Cs + 255) / 256 : 0);
-  const long grid = (long)k.ns * a.njobs + k.ne + k.nd + k.nz + k.np;
+  LBWN_REQUIRE(!a.ids || (a.tlive && a.klive && a.nklive && a.kpre), "step_prologue: bad live-list arguments");
+  k.nl = a.ids ? 1 : 0;
+  const long grid = (long)k.nl + (long)k.ns * a.njobs + k.ne + k.nd + k.nz + k.np;
   step_prologue_kernel<<<(unsigned)grid, 256, 0, st>>>(k);
   LBWN_CHECK_LAUNCH();
   return 0;

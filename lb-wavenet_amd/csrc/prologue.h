@@ -81,6 +81,72 @@ LBWN_DEV void zero_body(long blk, long nblk, unsigned* p, long n) {
   for (long e = blk * 256 + threadIdx.x; e < n; e += nblk * 256) p[e] = 0u;
 }
 
+// ---- live lists of the masked-position skip --------------------------------------------------
+// Row m = (b, t) of the step is valid iff t < T-1 and ids[min(m+1, M-1)] != 0 (misc.hip
+// head_reg_kernel; tmodel.py:231-232); the head writes dlogits = 0 at every other row, so the
+// backward's dH1 / dS / dZ rows there are exactly zero.  tlive[ceil(M/256)]: 1 = the 256-row tile
+// holds a valid row; klive: the ascending list of the 32-row k-steps that hold one, nklive its
+// length; kpre[k], k = 0 .. ceil(M/32): the number of list entries below k-step k (a split-K
+// slice's share of the list is kpre[its first k-step] .. kpre[its end]).  ONE block of 256 threads; a round covers 128 k-steps, 32 per wave: 16 loads of 64
+// consecutive ids per wave (a k-step per thread, 32 lines per lane, ran the block 30 us at C2 and
+// stretched the prologue 21 -> 30 us: every load touched 64 lines), all unconditional at clamped
+// indices and issued a round ahead of their use (two sets of 16 registers: 32 loads a set put the
+// whole prologue kernel at 100 VGPRs).  A load's ballot is two k-steps' flags; the list is
+// compacted from the flag words and a fixed-order sum of the four wave counts (no atomics: the
+// same list every run).
+LBWN_DEV void live_lists_body(const int* __restrict__ ids, int B, int T, int* tlive, int* klive, int* nklive,
+                              int* kpre) {
+  __shared__ int wcnt[4];
+  const int M = B * T, nk = (M + 31) / 32, nt = (M + 255) / 256;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int inc = 64 % T;   // t of a lane's next row (64 further)
+  constexpr int NL = 16, KW = 2 * NL, KR = 4 * KW;   // loads, k-steps per wave, k-steps per round
+  auto row0 = [&](int k0) { return 32 * (k0 + KW * w) + lane; };   // this lane's first row of the round
+  int v[NL], nx[NL];
+  auto load = [&](int (&d)[NL], int k0) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) d[j] = ids[min(row0(k0) + 64 * j + 1, M - 1)];
+  };
+  load(v, 0);
+  int base = 0;
+  for (int k0 = 0; k0 < nk; k0 += KR) {
+    load(nx, min(k0 + KR, nk));   // (past the end: clamped rows, unused)
+    const int r0 = row0(k0);
+    int t = r0 % T;
+    unsigned live = 0u;   // bit i = k-step k0 + 32w + i holds a valid row (wave-uniform)
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const unsigned long long bal = __ballot((r0 + 64 * j < M) & (t != T - 1) & (v[j] != 0));
+      live |= (unsigned)((unsigned)bal != 0u) << (2 * j);
+      live |= (unsigned)((bal >> 32) != 0ull) << (2 * j + 1);
+      t += inc;
+      t -= t >= T ? T : 0;
+    }
+    const int k = k0 + KW * w + lane;   // lanes 0..31
+    if (lane == 0) wcnt[w] = __popc(live);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      off += i < w ? wcnt[i] : 0;
+      tot += wcnt[i];
+    }
+    const int pos = off + __popc(live & ((1u << (lane & 31)) - 1u));
+    if (lane < KW && k < nk) kpre[k] = pos;
+    if (lane < KW && ((live >> lane) & 1u)) klive[pos] = k;
+    // a tile = 8 consecutive k-steps = 8 flag bits
+    if (lane < KW && (lane & 7) == 0 && (k >> 3) < nt) tlive[k >> 3] = ((live >> lane) & 0xffu) != 0u;
+    base += tot;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NL; ++j) v[j] = nx[j];
+  }
+  if (tid == 0) {
+    *nklive = base;
+    kpre[nk] = base;
+  }
+}
+
 // Pre-split planes of weights W (f32, row stride ldw): out[r][kc][plane][32] = split of
 // W[r][32·kc + j] (k-contiguous, trans = 0) or W[32·kc + j][r] (trans = 1); k ≥ K is zero.
 // Up to 6 weights per launch.

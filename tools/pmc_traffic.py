@@ -63,7 +63,7 @@ def gemm_key(gi, name):
     by their kernel form."""
     if gi < 8:
         return GEMM_ORDER[gi]
-    if 'gemm_x3q_kernel<8, true>' in name:
+    if 'gemm_x3q_kernel<8, true' in name:   # (<8, true, true>: over the live k-step list)
         return 'dskip'
     if gi == 8:
         return 'lc_wgrad'
