@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LBWN_ABI_VERSION 3
+#define LBWN_ABI_VERSION 4
 
 /* par/arch*.json after normalisation (tmodel.py:10-23, arch.py:31-103). */
 typedef struct lbwn_arch {
@@ -208,6 +208,75 @@ int lbwn_gemm_f32_presplit(const float* A, int64_t lda, int a_kcontig, const uin
  * W[r*ldw+k] (trans = 0) or W[k*ldw+r] (trans = 1), r < rows. */
 int64_t lbwn_split_planes_elems_abi(int rows, int K);
 int lbwn_split_planes(const float* W, int64_t ldw, int rows, int K, int trans, uint16_t* out, void* stream);
+
+/* The same product with every option of the step's GEMM launcher (ABI 4; for parity tests of the
+ * kernel forms and epilogues the two entries above cannot reach).  struct_size = sizeof(this struct)
+ * (else EINVAL); unused fields are zero.  A / B / C, strides, a_kcontig / b_kcontig, bias, mask,
+ * relu_a, relu_out, accumulate, split_k / slab_ws and b3 are those of lbwn_gemm_f32[_presplit]
+ * (b3 may be NULL: B is then split on the fly).  The rest, all optional, bf16-split mode only:
+ *   colpart   fp32 [ceil(M/256)][N] out: column sums of the final C per 256-row block (no split-K);
+ *             lbwn_colpart_parts_abi(M) rows.
+ *   step_advance  int64 device counter, +1 per launch.
+ *   c_chain_ls > 0: C in the backward chain's order instead of rows (ldc unused): 32-column block j
+ *             at C + j*c_chain_ls, element (m, c) of it at
+ *             ((((m >> 5)*4 + ((c >> 3) & 3))*32 + (m & 31))*8 + (c & 7)); needs N % 32 == 0,
+ *             c_chain_ls >= ceil(M/32)*1024, no split-K / accumulate / mask, and on the x3q forms
+ *             no bias / relu_out / mask bits either.
+ *   xcd2d     x3q<10> only: 2-D placement of the tiles over the XCDs (same values).
+ *   a_kstride A k-contiguous, lda = 32, K % 32 == 0: element (m, k) at A[m*32 + (k/32)*a_kstride + k%32].
+ *   b_gstride B n-contiguous, ldb = 32, no b3: element (k, n) at B[k*32 + (n/32)*b_gstride + n%32].
+ *   a_gstride A m-contiguous, lda = 32 (the x3q<6 / 8,amn> forms only, M >= 256, no bias / mask):
+ *             element (m, k) at A[k*32 + (m/32)*a_gstride + m%32].
+ *   row_exact every row is computed by the tall form whatever M is (a row's value depends only on
+ *             its own A row).
+ *   mbits_out / mbits  x3q<8> only, no split-K: uint64 [lbwn_gemm_mbits_words_abi(M, N)], bit =
+ *             (final C > 0) written by a producer; a consumer of the same shape and form masks by it.
+ *   row_live  x3q<8> / x3q<10> only, no split-K: int32 [ceil(M/256)], 0 = every A row of that
+ *             256-row tile is exactly zero (the tile skips its k-loop).
+ *   k_live / nk_live / k_pre  both operands mn-contiguous, K % 32 == 0, no b3: the ascending list of
+ *             the 32-deep k-steps whose B rows are not all zero, its length (int32[1]) and
+ *             k_pre[k] = number of list entries below k-step k (int32 [K/32 + 1]).
+ *   splits_deferred  host int out (nullable): the split-K partials stay unsummed in slab_ws
+ *             ([splits][M][N]) and the split count actually used is stored here (1: C was written);
+ *             plain products only.
+ * Combinations the chosen kernel would not honour are refused with EINVAL before any launch.
+ * (Not exposed: the one-hot A operand lbwn_gemm_args::a_codes and the lean launcher.) */
+typedef struct lbwn_gemm_ex_args {
+  size_t struct_size;
+  const float* A; const float* B; float* C;
+  int64_t lda, ldb, ldc;
+  int M, N, K;
+  int a_kcontig, b_kcontig, split_k;
+  float* slab_ws;
+  const float* bias; const float* mask;
+  int64_t ldm;
+  int relu_a, relu_out, accumulate, xcd2d;
+  const uint16_t* b3;
+  float* colpart;
+  int64_t* step_advance;
+  int64_t c_chain_ls, a_kstride, b_gstride, a_gstride;
+  uint64_t* mbits_out; const uint64_t* mbits;
+  const int* row_live; const int* k_live; const int* nk_live; const int* k_pre;
+  int* splits_deferred;
+  int row_exact, reserved;
+} lbwn_gemm_ex_args;
+int lbwn_gemm_ex(const lbwn_gemm_ex_args* a, void* stream);
+/* The kernel instantiation the most recent GEMM launch on this thread chose ("" when that call was
+ * refused before a launch; the string is static).  bf16-split mode:
+ *   "x3q<8>" "x3q<10>" "x3q<6>"                     A in registers, 256 x 128 / 160 / 96 tiles
+ *   "x3q<8,amn>" "x3q<8,amn,kl>" "x3q<6,amn>"       their weight-gradient forms (kl: over k_live)
+ *   "x3<A,B,K,W>"   LDS-staged: A = akc | amn, B = bkc | bmn | pre (b3), K = kfull (K % 32 == 0) |
+ *                   kany, W = wm2 (128-row tiles) | wm4 (256-row: row_exact, M >= 8192 or colpart)
+ *   "x3<kl>"        the 128-row form over k_live
+ * f32 mode: "f32<A,B>" with A = akc | amn, B = bkc | bmn. */
+const char* lbwn_gemm_last_form(void);
+int64_t lbwn_gemm_mbits_words_abi(int M, int N);
+int lbwn_colpart_parts_abi(int M);
+/* The launcher's own predicates for a product of this shape (1 / 0; -1 for another `which`):
+ * which 0: it runs "x3q<8>" (mbits / mbits_out allowed); 1: it runs "x3q<8>" or "x3q<10>"
+ * (row_live allowed); 2: k_live is allowed (both operands mn-contiguous assumed; only M, N, K are
+ * read). */
+int lbwn_gemm_form_query(int which, int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart);
 
 /* One residual layer forward (tmodel.py:117-184): x_in is the [B][H+T][n_res] halo
  * buffer whose rows [H-d, H) hold SAVE; writes z [M][*] (row stride ldz) and, if x_out,

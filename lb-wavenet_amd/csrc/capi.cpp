@@ -80,6 +80,39 @@ int lbwn_split_planes(const float* W, int64_t ldw, int rows, int K, int trans, u
   return lbwn_split_planes_launch(1, &W, &l, &rows, &K, &trans, &o, (hipStream_t)stream);
 }
 
+int lbwn_gemm_ex(const lbwn_gemm_ex_args* a, void* stream) {
+  LBWN_REQUIRE(a != nullptr, "gemm_ex: null argument struct");
+  LBWN_REQUIRE(a->struct_size == sizeof(lbwn_gemm_ex_args), "gemm_ex: struct_size %zu != %zu (another ABI?)",
+               a->struct_size, sizeof(lbwn_gemm_ex_args));
+  LBWN_REQUIRE(a->A && a->B && a->C, "gemm_ex: A, B or C is null");
+  lbwn_gemm_args g;
+  memset(&g, 0, sizeof(g));
+  g.A = a->A; g.lda = (long)a->lda; g.B = a->B; g.ldb = (long)a->ldb; g.C = a->C; g.ldc = (long)a->ldc;
+  g.M = a->M; g.N = a->N; g.K = a->K; g.bias = a->bias; g.mask = a->mask; g.ldm = (long)a->ldm;
+  g.relu_a = a->relu_a; g.relu_out = a->relu_out; g.accumulate = a->accumulate;
+  g.b3 = (const unsigned short*)a->b3; g.colpart = a->colpart; g.step_advance = (long long*)a->step_advance;
+  g.c_chain_ls = (long)a->c_chain_ls; g.xcd2d = a->xcd2d;
+  g.a_kstride = (long)a->a_kstride; g.b_gstride = (long)a->b_gstride; g.a_gstride = (long)a->a_gstride;
+  g.row_exact = a->row_exact;
+  g.mbits_out = (unsigned long long*)a->mbits_out; g.mbits = (const unsigned long long*)a->mbits;
+  g.row_live = a->row_live; g.k_live = a->k_live; g.nk_live = a->nk_live; g.k_pre = a->k_pre;
+  g.splits_deferred = a->splits_deferred;
+  return lbwn_gemm_launch(g, a->a_kcontig, a->b_kcontig, a->split_k, a->slab_ws, (hipStream_t)stream);
+}
+
+const char* lbwn_gemm_last_form(void) { return lbwn_gemm_last_form_impl(); }
+int64_t lbwn_gemm_mbits_words_abi(int M, int N) { return (int64_t)lbwn_gemm_mbits_words(M, N); }
+int lbwn_colpart_parts_abi(int M) { return lbwn_colpart_parts(M); }
+int lbwn_gemm_form_query(int which, int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart) {
+  switch (which) {
+    case 0: return lbwn_gemm_x3q8_form(M, N, K, a_kcontig, presplit, row_exact, colpart) ? 1 : 0;
+    case 1: return lbwn_gemm_row_live_form(M, N, K, a_kcontig, presplit, row_exact, colpart) ? 1 : 0;
+    case 2: return lbwn_gemm_k_live_form(M, N, K) ? 1 : 0;
+  }
+  lbwn_set_error("gemm_form_query: which must be 0 (x3q<8>), 1 (row_live) or 2 (k_live), got %d", which);
+  return -1;
+}
+
 int lbwn_gemm_set_mode(int mode) { return lbwn_gemm_set_mode_impl(mode); }
 int lbwn_gemm_get_mode(void) { return lbwn_gemm_mode(); }
 

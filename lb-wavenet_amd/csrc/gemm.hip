@@ -1185,6 +1185,10 @@ __global__ void split_planes_kernel(SplitJobs jb) { split_planes_body(jb, blockI
 }  // namespace
 
 namespace {
+// the kernel instantiation the most recent lbwn_gemm_launch on this thread chose (include/lbwn.h
+// lbwn_gemm_last_form): set at every launch site below, "" while a call has launched nothing
+thread_local const char* g_last_form = "";
+
 // shape checks and split-K set-up shared by both GEMM forms
 int gemm_setup(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int& split_k, float* slab_ws, int BK,
                int BM, int BN, lbwn_gemm_args& g, dim3& grid) {
@@ -1205,6 +1209,9 @@ int gemm_setup(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int& split
                                 a.K % 32 == 0 && !a.mask && !a.bias && !a.colpart && !a.c_chain_ls && !a.a_codes &&
                                 lbwn_gemm_mode() == 1),
                "gemm: mn-blocked A needs the AMN weight-gradient form (lda = 32, M >= 256, K %% 32 == 0)");
+  // (checked here, before the launch: the partials of a refused call are never written)
+  LBWN_REQUIRE(!a.splits_deferred || (!a.bias && !a.relu_out && !a.mask && !a.accumulate),
+               "gemm: deferred split-K needs a plain product");
   if (split_k < 1) split_k = 1;
   g = a;
   int kps = (a.K + split_k - 1) / split_k;
@@ -1226,7 +1233,6 @@ int gemm_setup(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int& split
 
 int splitk_finish(const lbwn_gemm_args& a, int split_k, const float* slab_ws, hipStream_t st) {
   if (a.splits_deferred) {   // the consumer sums the partials itself (lc_up_bwd_kernel)
-    LBWN_REQUIRE(!a.bias && !a.relu_out && !a.mask && !a.accumulate, "gemm: deferred split-K needs a plain product");
     *a.splits_deferred = split_k;
     return 0;
   }
@@ -1242,13 +1248,27 @@ int splitk_finish(const lbwn_gemm_args& a, int split_k, const float* slab_ws, hi
 template <bool KFULL, bool BPRE, int WM>
 int gemm_launch_x3_t(const lbwn_gemm_args& g, const dim3& grid, int a_kcontig, int b_kcontig, hipStream_t st) {
   constexpr int NTHR = 128 * WM, S = WM == 4 ? 2 : 1;
+#define X3_FORM(a, b)                                                                               \
+  (KFULL ? (WM == 4 ? "x3<" a "," b ",kfull,wm4>" : "x3<" a "," b ",kfull,wm2>")                    \
+         : (WM == 4 ? "x3<" a "," b ",kany,wm4>" : "x3<" a "," b ",kany,wm2>"))
   if (BPRE) {
+    g_last_form = a_kcontig ? X3_FORM("akc", "pre") : X3_FORM("amn", "pre");
     if (a_kcontig) gemm_x3_kernel<true, true, KFULL, true, WM, S><<<grid, NTHR, 0, st>>>(g);
     else gemm_x3_kernel<false, true, KFULL, true, WM, S><<<grid, NTHR, 0, st>>>(g);
-  } else if (a_kcontig && b_kcontig) gemm_x3_kernel<true, true, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
-  else if (a_kcontig) gemm_x3_kernel<true, false, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
-  else if (b_kcontig) gemm_x3_kernel<false, true, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
-  else gemm_x3_kernel<false, false, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
+  } else if (a_kcontig && b_kcontig) {
+    g_last_form = X3_FORM("akc", "bkc");
+    gemm_x3_kernel<true, true, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
+  } else if (a_kcontig) {
+    g_last_form = X3_FORM("akc", "bmn");
+    gemm_x3_kernel<true, false, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
+  } else if (b_kcontig) {
+    g_last_form = X3_FORM("amn", "bkc");
+    gemm_x3_kernel<false, true, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
+  } else {
+    g_last_form = X3_FORM("amn", "bmn");
+    gemm_x3_kernel<false, false, KFULL, false, WM, S><<<grid, NTHR, 0, st>>>(g);
+  }
+#undef X3_FORM
   LBWN_CHECK_LAUNCH();
   return 0;
 }
@@ -1262,6 +1282,12 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
                "gemm (bf16 split): chain-order C needs split_k = 1, no accumulate/mask, N %% 32 == 0");
   LBWN_REQUIRE(a.b3 == nullptr || (a.K % X3_BK == 0 && (((uintptr_t)a.b3) & 15) == 0),
                "gemm (bf16 split): pre-split B needs K %% 32 == 0 and 16-B alignment");
+  // gemm_x3q_kernel's chain-order epilogue stores the raw accumulators (dZ: a plain product): the
+  // launches that reach it (the dispatch below) take no option it would drop
+  LBWN_REQUIRE(!a.c_chain_ls || !(a.bias || a.relu_out || a.mbits || a.mbits_out) ||
+                   !(X3Q && X3R && a_kcontig && a.b3 && (a.colpart || (a.N <= 2048 && (a.M >= 8192 || a.row_exact)))),
+               "gemm (bf16 split): chain-order C on the A-in-registers form (gemm_x3q_kernel) takes no bias / relu_out / "
+               "mask bits");
   LBWN_REQUIRE(!(a.mbits || a.mbits_out) ||
                    (lbwn_gemm_x3q8_form(a.M, a.N, a.K, a_kcontig, a.b3 != nullptr, a.row_exact, a.colpart != nullptr) &&
                     split_k <= 1),
@@ -1291,6 +1317,7 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
     // 355 us, dPOST1 split 32 97 vs 107; dPOST2 (4 tiles) 87 vs 77 stays on the 2-per-CU kernel.
     // N <= 96 (dLCcat as DVᵀ·lc, N = n_lc_out): 96-column tiles
     if ((e = gemm_setup(a, a_kcontig, b_kcontig, split_k, slab_ws, X3_BK, 256, a.N <= 96 ? 96 : 128, g, grid))) return e;
+    g_last_form = a.N <= 96 ? "x3q<6,amn>" : klist ? "x3q<8,amn,kl>" : "x3q<8,amn>";
     if (a.N <= 96) gemm_x3q_kernel<6, true><<<grid, 512, 0, st>>>(g);
     else if (klist) gemm_x3q_kernel<8, true, true><<<grid, 512, 0, st>>>(g);
     else gemm_x3q_kernel<8, true><<<grid, 512, 0, st>>>(g);
@@ -1304,6 +1331,7 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
   if (wm == 4 && X3R && kfull && pre && a_kcontig) {
     if (a.N <= 96) {   // 96-column tiles: the grid is re-formed for them
       grid.x = (unsigned)(((a.M + 255) / 256) * ((a.N + 95) / 96));
+      g_last_form = X3Q ? "x3q<6>" : "x3r<3>";
       if (X3Q) gemm_x3q_kernel<6><<<grid, 512, 0, st>>>(g);
       else gemm_x3r_kernel<3><<<grid, 512, 0, st>>>(g);
     } else if (X3Q && a.N % 160 == 0 && a.N > 512) {
@@ -1312,10 +1340,13 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
       // 1664 = 6.5 rounds; same box 2.296-2.304 vs 2.342-2.353 ms per step).
       // a.xcd2d (the caller's choice): the 2-D XCD blocking of the tiles (xcd2d_tile)
       grid.x = (unsigned)(((a.M + 255) / 256) * (a.N / 160));
+      g_last_form = "x3q<10>";
       gemm_x3q_kernel<10><<<grid, 512, 0, st>>>(g);
     } else if (X3Q) {   // (lbwn_gemm_x3q8_form)
+      g_last_form = "x3q<8>";
       gemm_x3q_kernel<8><<<grid, 512, 0, st>>>(g);
     } else {
+      g_last_form = "x3r<4>";
       gemm_x3r_kernel<4><<<grid, 512, 0, st>>>(g);
     }
     LBWN_CHECK_LAUNCH();
@@ -1324,6 +1355,7 @@ int gemm_launch_x3(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int sp
     else if (kfull) e = gemm_launch_x3_t<true, false, 4>(g, grid, a_kcontig, b_kcontig, st);
     else e = gemm_launch_x3_t<false, false, 4>(g, grid, a_kcontig, b_kcontig, st);
   } else if (klist) {   // (lbwn_gemm_k_live_form: both operands mn-contiguous, K % 32 == 0, no pre-split)
+    g_last_form = "x3<kl>";
     gemm_x3_kernel<false, false, true, false, 2, 1, true><<<grid, 256, 0, st>>>(g);
     LBWN_CHECK_LAUNCH();
   } else {
@@ -1341,6 +1373,7 @@ int gemm_launch_t(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int spl
   dim3 grid;
   int e = gemm_setup(a, a_kcontig, b_kcontig, split_k, slab_ws, BK, BMT, BNT, g, grid);
   if (e) return e;
+  g_last_form = a_kcontig ? (b_kcontig ? "f32<akc,bkc>" : "f32<akc,bmn>") : (b_kcontig ? "f32<amn,bkc>" : "f32<amn,bmn>");
   if (a_kcontig && b_kcontig) gemm_f32_kernel<true, true, BK, BMT, BNT><<<grid, NT, 0, st>>>(g);
   else if (a_kcontig) gemm_f32_kernel<true, false, BK, BMT, BNT><<<grid, NT, 0, st>>>(g);
   else if (b_kcontig) gemm_f32_kernel<false, true, BK, BMT, BNT><<<grid, NT, 0, st>>>(g);
@@ -1385,11 +1418,15 @@ bool lbwn_gemm_k_live_form(int M, int N, int K) {
   return lbwn_gemm_mode() == 1 && M >= 4 && N >= 4 && K >= 4 && K % X3_BK == 0 && N % 4 == 0 && !(amn && N <= 96);
 }
 
+const char* lbwn_gemm_last_form_impl(void) { return g_last_form; }
+
 int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
                      hipStream_t st) {
+  g_last_form = "";
   if (lbwn_gemm_mode() == 1 && a.a_codes == nullptr && a.K >= 4 && a.M >= 4 && a.N >= 4)
     return gemm_launch_x3(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
   LBWN_REQUIRE(!a.row_live && !a.k_live && !a.nk_live && !a.k_pre, "gemm: row_live / k_live need the bf16-split form");
+  LBWN_REQUIRE(!a.mbits && !a.mbits_out, "gemm: mask bits need the bf16-split form");
   LBWN_REQUIRE(a.colpart == nullptr && a.step_advance == nullptr && !a.c_chain_ls,
                "gemm: column partials / the step counter / chain-order C need the bf16-split form");
   return gemm_launch_t<16, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
@@ -1397,9 +1434,11 @@ int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int 
 
 int lbwn_gemm_launch_lean(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
                           hipStream_t st) {
+  g_last_form = "";
   if (lbwn_gemm_mode() == 1 && a.a_codes == nullptr && a.K >= 4 && a.M >= 4 && a.N >= 4)
     return gemm_launch_x3(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
   LBWN_REQUIRE(!a.row_live && !a.k_live && !a.nk_live && !a.k_pre, "gemm: row_live / k_live need the bf16-split form");
+  LBWN_REQUIRE(!a.mbits && !a.mbits_out, "gemm: mask bits need the bf16-split form");
   LBWN_REQUIRE(a.colpart == nullptr, "gemm: column partials need the bf16-split form");
   return gemm_launch_t<8, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
 }

@@ -21,7 +21,9 @@ struct lbwn_gemm_args {
   long long* step_advance;   // nullable, bf16-split form only: block 0 adds 1 (the per-step generator's counter)
   // bf16-split form, no split-K / accumulate / mask: > 0 stores C in the backward chain's row-load
   // order instead of rows (ldc unused): 32-column block j at C + j·c_chain_ls, element (m, c) at
-  // sg_off(m, c / 8, (c / 4) & 1) + c % 4 (layer.hip), so the chain's own-row loads are 1-KiB runs
+  // sg_off(m, c / 8, (c / 4) & 1) + c % 4 (layer.hip), so the chain's own-row loads are 1-KiB runs.
+  // The A-in-registers forms (gemm_x3q_kernel) store the raw sums in this order: there the launcher
+  // also refuses bias / relu_out / mbits / mbits_out; the LDS-staged forms apply bias and relu_out
   long c_chain_ls;
   int k_per_split;     // set by the launcher
   int* splits_deferred;   // host, nullable: split-K partials left unsummed in the slab workspace
@@ -69,6 +71,9 @@ bool lbwn_gemm_x3q8_form(int M, int N, int K, int a_kcontig, int presplit, int r
 inline long lbwn_gemm_mbits_words(long M, long N) { return ((M + 255) / 256) * ((N + 127) / 128) * 8 * 64; }
 int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
                      hipStream_t st);
+// the kernel instantiation the most recent lbwn_gemm_launch / _lean on this thread chose (the names
+// of include/lbwn.h lbwn_gemm_last_form; "" while the call has launched nothing)
+const char* lbwn_gemm_last_form_impl(void);
 inline int lbwn_colpart_parts(long M) { return (int)((M + 255) / 256); }
 // Pre-split planes of a weight for lbwn_gemm_args::b3: rows = N of the product it feeds,
 // W[r][k] (trans = 0) or W[k][r] (trans = 1), row stride ldw; up to 6 weights per launch.

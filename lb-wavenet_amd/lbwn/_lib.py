@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the .so: shared HIP runtime)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'liblbwn.so')   # the in-tree build only (tools/with_lib.py loads variants)
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 c_int, c_int64, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_fp = ctypes.c_void_p   # device pointers are passed as integers
@@ -34,6 +34,26 @@ class Params(ctypes.Structure):
         'pre', 'pre_b', 'sig', 'sig_b', 'gate', 'gate_b', 'res', 'res_b', 'skip', 'skip_b',
         'gc_embed', 'gc_sig', 'gc_gate', 'lc_sig', 'lc_gate')] + [('lc_up', c_fp * 8)] + [
         (n, c_fp) for n in ('post1', 'post1_b', 'post2', 'post2_b')]
+
+
+class GemmExArgs(ctypes.Structure):
+    """lbwn_gemm_ex_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('A', c_fp), ('B', c_fp), ('C', c_fp),
+                ('lda', c_int64), ('ldb', c_int64), ('ldc', c_int64),
+                ('M', c_int), ('N', c_int), ('K', c_int),
+                ('a_kcontig', c_int), ('b_kcontig', c_int), ('split_k', c_int),
+                ('slab_ws', c_fp), ('bias', c_fp), ('mask', c_fp), ('ldm', c_int64),
+                ('relu_a', c_int), ('relu_out', c_int), ('accumulate', c_int), ('xcd2d', c_int),
+                ('b3', c_fp), ('colpart', c_fp), ('step_advance', c_fp),
+                ('c_chain_ls', c_int64), ('a_kstride', c_int64), ('b_gstride', c_int64), ('a_gstride', c_int64),
+                ('mbits_out', c_fp), ('mbits', c_fp),
+                ('row_live', c_fp), ('k_live', c_fp), ('nk_live', c_fp), ('k_pre', c_fp),
+                ('splits_deferred', ctypes.POINTER(c_int)),
+                ('row_exact', c_int), ('reserved', c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(GemmExArgs)
 
 
 _SIGS = {
@@ -68,6 +88,11 @@ _SIGS = {
                                        c_int, c_fp, c_int, c_int, c_fp, c_int64, c_int, c_void_p]),
     'lbwn_split_planes_elems_abi': (c_int64, [c_int, c_int]),
     'lbwn_split_planes': (c_int, [c_fp, c_int64, c_int, c_int, c_int, c_fp, c_void_p]),
+    'lbwn_gemm_ex': (c_int, [ctypes.POINTER(GemmExArgs), c_void_p]),
+    'lbwn_gemm_last_form': (ctypes.c_char_p, []),
+    'lbwn_gemm_mbits_words_abi': (c_int64, [c_int, c_int]),
+    'lbwn_colpart_parts_abi': (c_int, [c_int]),
+    'lbwn_gemm_form_query': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'lbwn_gemm_set_mode': (c_int, [c_int]),
     'lbwn_gemm_get_mode': (c_int, []),
     'lbwn_layer_image_floats_abi': (c_int, []),

@@ -24,6 +24,42 @@ def test_library_loads_and_exports_header_symbols():
     assert lib.lbwn_abi_version() == _lib.ABI_VERSION
 
 
+def test_gemm_ex_struct_size_and_queries_without_gpu():
+    """lbwn_gemm_ex_args: the ctypes mirror has the header's fields in the header's order and the
+    size the library was compiled with (the entry names its own sizeof when it refuses another);
+    the argument checks and the shape queries run before any device work."""
+    import ctypes
+    from lbwn import _lib
+    lib = _lib.load()
+    txt = open(os.path.join(ROOT, 'include', 'lbwn.h')).read()
+    body = re.search(r'typedef struct lbwn_gemm_ex_args \{(.*?)\} lbwn_gemm_ex_args;', txt, re.S).group(1)
+    fields = [re.findall(r'\w+', piece)[-1] for decl in body.split(';') for piece in decl.split(',') if piece.strip()]
+    assert fields == [n for n, _ in _lib.GemmExArgs._fields_], fields
+    a = _lib.GemmExArgs()
+    size = ctypes.sizeof(_lib.GemmExArgs)
+    assert a.struct_size == size
+    for bad in (0, size - 8, size + 8):
+        a.struct_size = bad
+        assert lib.lbwn_gemm_ex(ctypes.byref(a), None) == 22
+        assert b'struct_size %d != %d' % (bad, size) in lib.lbwn_last_error(), lib.lbwn_last_error()
+    a.struct_size = size
+    assert lib.lbwn_gemm_ex(ctypes.byref(a), None) == 22       # right size: the next check speaks
+    assert b'null' in lib.lbwn_last_error() and b'struct_size' not in lib.lbwn_last_error()
+    assert lib.lbwn_gemm_last_form() == b''
+    assert lib.lbwn_gemm_mbits_words_abi(520, 136) == 3 * 2 * 8 * 64
+    assert lib.lbwn_colpart_parts_abi(520) == 3 and lib.lbwn_colpart_parts_abi(512) == 2
+    # (which, M, N, K, a_kcontig, presplit, row_exact, colpart)
+    assert lib.lbwn_gemm_form_query(0, 520, 136, 96, 1, 1, 1, 0) == 1
+    assert lib.lbwn_gemm_form_query(0, 520, 136, 96, 1, 1, 0, 0) == 0
+    assert lib.lbwn_gemm_form_query(0, 520, 640, 64, 1, 1, 1, 0) == 0
+    assert lib.lbwn_gemm_form_query(1, 520, 640, 64, 1, 1, 1, 0) == 1
+    assert lib.lbwn_gemm_form_query(1, 520, 80, 64, 1, 1, 1, 0) == 0
+    assert lib.lbwn_gemm_form_query(2, 1028, 200, 96, 0, 0, 0, 0) == 1
+    assert lib.lbwn_gemm_form_query(2, 1800, 80, 64, 0, 0, 0, 0) == 0
+    assert lib.lbwn_gemm_form_query(2, 260, 136, 100, 0, 0, 0, 0) == 0
+    assert lib.lbwn_gemm_form_query(3, 260, 136, 96, 0, 0, 0, 0) == -1
+
+
 def test_recep_field_via_capi():
     from lbwn import _lib
     import ctypes
