@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define LBWN_ABI_VERSION 4
+#define LBWN_ABI_VERSION 5
 
 /* par/arch*.json after normalisation (tmodel.py:10-23, arch.py:31-103). */
 typedef struct lbwn_arch {
@@ -175,6 +175,31 @@ int lbwn_gen_run(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace
  * own 32 head blocks, while every block fits on the device: B <= 80 on 256 CUs; layer/head sizes fit;
  * LBWN_GEN_PERSIST=0 at plan creation selects the per-step launches), else 0. */
 int lbwn_gen_is_persistent(const lbwn_gen_plan* plan);
+/* Advance every stream by n steps whose inputs are already known, in parallel over the n positions
+ * (ABI 5; the state n teacher-forced lbwn_gen_run steps leave, computed as a training-style forward).
+ * codes: device int32, stream b's j-th code at codes[b*ld_codes + j], j < n; ld_codes == 0: one
+ * vector shared by all streams (the reference's teacher_vec).
+ * With t0 the device step counter at the call, step t0 takes the pending input (the previous draw or
+ * prefilled code; the zero vector right after lbwn_gen_start) and step t0+j, j >= 1, takes
+ * codes[b][j-1]; PRE_BIAS is added as lbwn_gen_start's pre_bias says.  Afterwards every layer's ring
+ * holds x_l of the last min(d_l, t0+n) steps (slot t mod d_l), the pending input is codes[b][n-1], and
+ * the step counter (every persistent stream group's included) is t0+n.  For t0+j < max_steps,
+ * "samples"[b][t0+j] = codes[b][j] and "wav" its mu-law decode: the output holds the prompt followed by
+ * the continuation.  (On purpose unlike the teacher vector of lbwn_gen_start, whose steps store the
+ * model's ignored draws there.)  "logits" is not touched.  The uniform of step t stays
+ * splitmix64(seed, stream, t), so lbwn_gen_start without a teacher + prefill(c, n) + run(k) draws at
+ * steps n..n+k-1 what lbwn_gen_start(teacher = c, n) + run(n+k) draws there, up to fp32 rounding of
+ * the logits (a draw can differ only at a near tie of the CDF).
+ * Stream-ordered, no host synchronisation or allocation, graph-capturable (t0 is read on the device);
+ * may be called at t0 = 0 or in the middle of a run, any number of times.  The positions are
+ * processed in slices of T_s = the largest multiple of 128 with batch_sz*T_s <= 32768 (at least 128;
+ * env LBWN_GEN_PREFILL_SLICE=<integer 1..65536> at plan creation overrides it, anything else is
+ * EINVAL there); the scratch, carved at plan creation, does not grow with n.
+ * EINVAL before any launch: a null argument, n < 1, ld_codes neither 0 nor >= n, an arch with local
+ * conditioning, batch_sz*T_s*n_res >= 2^31.  Codes outside [0, n_quant) are the caller's error; they
+ * are clamped into it. */
+int lbwn_gen_prefill(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* codes,
+                     int64_t ld_codes, int64_t n, void* stream);
 
 /* ---- fine-grained kernels (parity tests, custom drivers) ------------------------------ */
 /* ops.mu_encode_np (ops.py:23-28, tf32=0, float64 math) / ops.mu_encode (ops.py:4-9, tf32=1) */

@@ -19,6 +19,9 @@
 // step kernels' loaders DMA that step's row into the fourth bias row of each layer's LDS slot.
 // Both draw with the same wave-level inverse-CDF code: u = hash(seed, stream, step), µ-law
 // decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).
+// Prompt prefill (lbwn_gen_prefill): n steps with known inputs as a sliced per-layer forward
+// (layer.hip's layer_fwd_kernel) whose D-separation state is the rings; its kernels are at the end
+// of the namespace below, the step kernels know nothing of it.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1176,6 +1179,130 @@ __global__ void gen_reset_kernel(float* rings, long n_ring, unsigned long long* 
   }
 }
 
+// ---- parallel prompt prefill (lbwn_gen_prefill) -------------------------------
+// n steps whose inputs are known are a training-style forward over n positions: per slice of T
+// positions, layer by layer through layer_fwd_kernel on two ping-pong halo buffers [B][H+T][Cr].
+// The generator's rings are the D-separation state between slices: layer l's halo rows [H-d, H) are
+// the ring slots of steps t0s-d .. t0s-1 (slots never written since gen_reset are zero = the
+// reference's zero lookback, so negative times need no case), and the slice's last min(d, T) inputs
+// go back into the ring.  t0s = *step + off: the step counter is only read until the finish kernel.
+
+// an input code as the step kernels may read it: pending -1 stays "zero vector", the rest inside PRE
+LBWN_DEV int prefill_clamp(int c, int Q) { return min(max(c, 0), Q - 1); }
+
+// layer 0's body rows of the slice: row j = PRE[in_j] (+ PRE_BIAS), in_j = the input of step
+// t0 + off + j: the pending code[b] for the call's first step, else codes[b][off + j - 1];
+// ids[b][j] = b (the per-stream GC table's row).  V4: one float4 per item (Cr % 4 == 0, aligned).
+struct PrefillE {
+  const float* pre; const float* pre_b; const int* codes; const int* code; float* x; int* ids;
+  long ld_codes, off;
+  int B, T, H, Cr, Q, bias;
+};
+template <bool V4>
+__global__ void gen_prefill_embed_kernel(PrefillE a) {
+  const int cw = V4 ? a.Cr >> 2 : a.Cr;
+  const long total = (long)a.B * a.T * cw;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(e % cw);
+    const long r = e / cw;
+    const int j = (int)(r % a.T), b = (int)(r / a.T);
+    const long g = a.off + j;
+    int q = g == 0 ? a.code[b] : a.codes[(long)b * a.ld_codes + g - 1];
+    if (g > 0 || q >= 0) q = prefill_clamp(q, a.Q);
+    float* dst = a.x + ((long)b * (a.H + a.T) + a.H + j) * a.Cr;
+    if (V4) {
+      floatx4 v = {0.f, 0.f, 0.f, 0.f};
+      if (q >= 0) v = *(const floatx4*)(a.pre + (long)q * a.Cr + 4 * c);
+      if (a.bias) v += *(const floatx4*)(a.pre_b + 4 * c);
+      *(floatx4*)(dst + 4 * c) = v;
+    } else {
+      float v = q >= 0 ? a.pre[(long)q * a.Cr + c] : 0.f;
+      if (a.bias) v += a.pre_b[c];
+      dst[c] = v;
+    }
+    if (c == 0 && a.ids) a.ids[(long)b * a.T + j] = b;
+  }
+}
+
+// Two independent copies of one slice in one launch (either may be absent):
+//   gen_body_to_ring  the last min(dw, T) body rows of layer l's input -> their slots of ring l
+//   gen_ring_to_halo  ring l+1's slots of steps t0s-dr .. t0s-1 -> halo rows [H-dr, H) of layer l+1's input
+// They touch different layers' rings and different buffers.  For ONE layer the halo copy comes a
+// launch earlier in stream order than the ring write: with T < d the slots written (steps t0s ..)
+// alias the oldest slots the halo copy reads (steps t0s-d ..).
+struct PrefillX {
+  const long long* step; long off;
+  const float* src; float* ring_w; int dw;
+  const float* ring_r; float* dst; int dr;
+  int B, T, H, Cr;
+};
+template <bool V4>
+__global__ void gen_prefill_xfer_kernel(PrefillX a) {
+  const int cw = V4 ? a.Cr >> 2 : a.Cr;
+  const long long t0s = *a.step + a.off;
+  const int nw = a.ring_w ? min(a.dw, a.T) : 0, nr = a.ring_r ? a.dr : 0;
+  const long tw = (long)a.B * nw * cw, total = tw + (long)a.B * nr * cw;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const float* s;
+    float* d;
+    if (e < tw) {   // body -> ring
+      const int c = (int)(e % cw);
+      const long r = e / cw;
+      const int i = (int)(r % nw), b = (int)(r / nw), j = a.T - nw + i;
+      const long slot = (long)((t0s + j) & (long long)(a.dw - 1));
+      s = a.src + ((long)b * (a.H + a.T) + a.H + j) * a.Cr;
+      d = a.ring_w + ((long)b * a.dw + slot) * a.Cr;
+      if (V4) *(floatx4*)(d + 4 * c) = *(const floatx4*)(s + 4 * c);
+      else d[c] = s[c];
+    } else {        // ring -> halo
+      const long f = e - tw;
+      const int c = (int)(f % cw);
+      const long r = f / cw;
+      const int i = (int)(r % nr), b = (int)(r / nr);
+      const long slot = (long)((t0s - a.dr + i) & (long long)(a.dr - 1));   // two's complement: also for t < 0
+      s = a.ring_r + ((long)b * a.dr + slot) * a.Cr;
+      d = a.dst + ((long)b * (a.H + a.T) + a.H - a.dr + i) * a.Cr;
+      if (V4) *(floatx4*)(d + 4 * c) = *(const floatx4*)(s + 4 * c);
+      else d[c] = s[c];
+    }
+  }
+}
+
+// the per-stream GC rows of the step kernels (gc_proj [L][B][sig 32 | gate 32]) as layer_fwd's table
+// [L][B][sig Cd | gate Cd]: the same sums the sequential path adds
+__global__ void gen_prefill_gctab_kernel(const float* gc_proj, float* out, long rows, int Cd) {
+  const long total = rows * 2 * Cd;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const int o = (int)(e % (2 * Cd));
+    out[e] = gc_proj[(e / (2 * Cd)) * 64 + (o < Cd ? o : 32 + o - Cd)];
+  }
+}
+
+// outputs of the prefilled steps: samples = the prompt, wav = its µ-law decode (the counter is only read)
+__global__ void gen_prefill_out_kernel(const int* codes, long ld_codes, long n, const long long* step, int* samples,
+                                       float* wav, long long max_steps, int B, int Q) {
+  const long long t0 = *step;
+  const long long span = min((long long)n, max(max_steps - t0, 0LL));
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < (long long)B * span;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long b = e / span, j = e % span;
+    const int q = prefill_clamp(codes[b * ld_codes + j], Q);
+    samples[b * max_steps + t0 + j] = q;
+    wav[b * max_steps + t0 + j] = mu_decode_q(q, Q);
+  }
+}
+
+// last launch of a prefill, one block: the pending input, the plan's step counter and the
+// persistent groups' (gstep[g-1], g = 1 .. ngroups-1)
+__global__ void gen_prefill_finish_kernel(const int* codes, long ld_codes, long n, int* code, long long* step,
+                                          long long* gstep, int ngroups, int B, int Q) {
+  const long long t1 = *step + n;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) code[b] = prefill_clamp(codes[(long)b * ld_codes + n - 1], Q);
+  __syncthreads();   // every thread has read *step
+  for (int g = threadIdx.x; g < ngroups - 1; g += blockDim.x) gstep[g] = t1;
+  if (threadIdx.x == 0) *step = t1;
+}
+
 }  // namespace
 
 // ---- host side: generation plan ----------------------------------------------------------
@@ -1208,10 +1335,17 @@ struct lbwn_gen_plan {
   long long hop = 1, lc_rows = 0;
   size_t oLC = 0, oLCACT[8] = {0, 0, 0, 0, 0, 0, 0, 0}, oLCC = 0;
   bool up_fused = false, mel_loaded = false;
+  // prefill (lbwn_gen_prefill): slice length, halo, and the scratch -- two halo
+  // buffers [B][pfH + pfT][Cr], z [B·pfT][Cd], the L packed layer images, the per-stream GC table
+  // [L][B][2·Cd] and ids [B][pfT]
+  int pfT = 0, pfH = 0;
+  size_t oPFX[2] = {0, 0}, oPFZ = 0, oPFIMG = 0, oPFGC = 0, oPFIDS = 0;
 };
 
 constexpr int G_LC_CHUNK = 64;         // default NC (steps per projection launch / persistent sub-run)
 constexpr int G_LC_CHUNK_MAX = 4096;
+constexpr int G_PF_ROWS = 32768;       // default prefill slice: B·T_s rows per layer launch (the C2 launch size)
+constexpr int G_PF_SLICE_MAX = 65536;
 
 // the per-step GEMM form: large B, shapes the split GEMM takes (N % 4, K % 4, row strides)
 static bool gemm_form_ok(const lbwn_gen_plan* p) {
@@ -1252,6 +1386,15 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     }
     LBWN_REQUIRE((long long)lc_chunk * B / LCP_ROWS < 65535, "gen: LBWN_GEN_LC_CHUNK %d x batch_sz %d is too large",
                  lc_chunk, B);   // the projection's grid: one block row per LCP_ROWS (step, stream) pairs
+  }
+  // prefill slice length: the largest multiple of 128 with B·T_s <= G_PF_ROWS, at least 128
+  int pf_slice = std::max(LBWN_LAYER_POS, G_PF_ROWS / B / LBWN_LAYER_POS * LBWN_LAYER_POS);
+  if (const char* pe = getenv("LBWN_GEN_PREFILL_SLICE")) {
+    char* end = nullptr;
+    const long v = strtol(pe, &end, 10);
+    LBWN_REQUIRE(end != pe && *end == 0 && v >= 1 && v <= G_PF_SLICE_MAX,
+                 "gen: LBWN_GEN_PREFILL_SLICE must be an integer in 1..%d (got '%s')", G_PF_SLICE_MAX, pe);
+    pf_slice = (int)v;
   }
   lbwn_gen_plan* p = new lbwn_gen_plan();
   p->a = *a;
@@ -1325,6 +1468,18 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     p->oLCACT[p->nup - 1] = p->oLC;
     p->oLCC = gcarve(cur, 4 * (size_t)p->NC * p->L * B * 64);
     p->up_fused = lbwn_lc_up_fused_ok(p->nup, p->up, p->Li, p->Lo) != 0;
+  }
+  {   // prefill scratch: independent of the prompt length (LC plans, which prefill refuses, carve it
+      // too: a plan's workspace is that of the same arch without LC plus the LC tensors)
+    p->pfT = pf_slice;
+    p->pfH = 1 << (p->nbl - 1);
+    for (int i = 0; i < 2; ++i) p->oPFX[i] = gcarve(cur, 4 * (size_t)B * ((size_t)p->pfH + p->pfT) * p->Cr);
+    p->oPFZ = gcarve(cur, 4 * (size_t)B * p->pfT * p->Cd);
+    p->oPFIMG = gcarve(cur, 4 * (size_t)p->L * lbwn_layer_image_floats());
+    if (a->n_gc_embed > 0) {
+      p->oPFGC = gcarve(cur, 4 * (size_t)p->L * B * 2 * p->Cd);
+      p->oPFIDS = gcarve(cur, 4 * (size_t)B * p->pfT);
+    }
   }
   p->total = cur;
   *out = p;
@@ -1583,5 +1738,89 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
         p->Q);
     LBWN_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// ---- parallel prompt prefill ----------------------------------------------------------------
+extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const int* codes, int64_t ld_codes,
+                                int64_t n, void* stream) {
+  LBWN_REQUIRE(p && P && ws && codes, "prefill: null argument");
+  LBWN_REQUIRE(n >= 1, "prefill: n must be >= 1 (got %lld)", (long long)n);
+  LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "prefill: ld_codes %lld must be 0 (one shared vector) or >= n = %lld",
+               (long long)ld_codes, (long long)n);
+  LBWN_REQUIRE(p->Lo == 0, "prefill: local conditioning is not supported");
+  LBWN_REQUIRE((long long)p->B * p->pfT * p->Cr < (1LL << 31), "prefill: batch_sz %d x slice %d x n_res %d >= 2^31",
+               p->B, p->pfT, p->Cr);
+  hipStream_t st = (hipStream_t)stream;
+  const int B = p->B, L = p->L, H = p->pfH, Cr = p->Cr, Cd = p->Cd;
+  float* X[2] = {gat<float>(ws, p->oPFX[0]), gat<float>(ws, p->oPFX[1])};
+  float* Z = gat<float>(ws, p->oPFZ);
+  float* img = gat<float>(ws, p->oPFIMG);
+  float* rings = gat<float>(ws, p->oRING);
+  long long* step = gat<long long>(ws, p->oSTEP);
+  int* code = gat<int>(ws, p->oCODE);
+  const bool gc = p->a.n_gc_embed > 0;
+  float* gtab = gc ? gat<float>(ws, p->oPFGC) : nullptr;
+  int* ids = gc ? gat<int>(ws, p->oPFIDS) : nullptr;
+  const bool bias = p->pre_bias && P->pre_b;
+  // float4 rows: the buffers and rings are 256-B carved and every ring offset is a multiple of Cr
+  const bool xv4 = Cr % 4 == 0 && (((uintptr_t)ws) & 15) == 0;
+  const bool ev4 = xv4 && (((uintptr_t)P->pre) & 15) == 0 && (!bias || (((uintptr_t)P->pre_b) & 15) == 0);
+  auto grid = [](long items) { return (int)std::max(1L, std::min(2048L, (items + 255) / 256)); };
+  if (int e = lbwn_pack_layers_launch(P->sig, P->gate, P->sig_b, P->gate_b, P->res, P->res_b, img, L, Cr, Cd, st))
+    return e;
+  if (gc) {
+    gen_prefill_gctab_kernel<<<grid((long)L * B * 2 * Cd), 256, 0, st>>>(gat<float>(ws, p->oGCP), gtab, (long)L * B, Cd);
+    LBWN_CHECK_LAUNCH();
+  }
+  const int WI = lbwn_layer_image_floats();
+  for (int64_t off = 0; off < n; off += p->pfT) {
+    const int T = (int)std::min<int64_t>(p->pfT, n - off);
+    PrefillE e;
+    e.pre = P->pre; e.pre_b = P->pre_b; e.codes = codes; e.code = code; e.x = X[0]; e.ids = ids;
+    e.ld_codes = (long)ld_codes; e.off = (long)off;
+    e.B = B; e.T = T; e.H = H; e.Cr = Cr; e.Q = p->Q; e.bias = bias ? 1 : 0;
+    if (ev4) gen_prefill_embed_kernel<true><<<grid((long)B * T * (Cr / 4)), 256, 0, st>>>(e);
+    else gen_prefill_embed_kernel<false><<<grid((long)B * T * Cr), 256, 0, st>>>(e);
+    LBWN_CHECK_LAUNCH();
+    long roff = 0;   // ring offset of layer l
+    for (int l = -1; l < L; ++l) {
+      // launch l: the ring write of layer l and the halo of layer l + 1 (whose buffer layer l - 1 has read)
+      PrefillX x;
+      memset(&x, 0, sizeof(x));
+      x.step = step; x.off = (long)off; x.B = B; x.T = T; x.H = H; x.Cr = Cr;
+      long items = 0;
+      if (l >= 0) {
+        x.dw = 1 << (l % p->nbl);
+        x.src = X[l & 1]; x.ring_w = rings + roff;
+        items += (long)B * std::min(x.dw, T);
+        roff += (long)x.dw * B * Cr;
+      }
+      if (l + 1 < L) {
+        x.dr = 1 << ((l + 1) % p->nbl);
+        x.ring_r = rings + roff; x.dst = X[(l + 1) & 1];
+        items += (long)B * x.dr;
+      }
+      if (xv4) gen_prefill_xfer_kernel<true><<<grid(items * (Cr / 4)), 256, 0, st>>>(x);
+      else gen_prefill_xfer_kernel<false><<<grid(items * Cr), 256, 0, st>>>(x);
+      LBWN_CHECK_LAUNCH();
+      if (l < 0) continue;
+      lbwn_layer_args a;
+      memset(&a, 0, sizeof(a));
+      a.x_in = X[l & 1]; a.x_out = l + 1 < L ? X[(l + 1) & 1] : nullptr;   // the last layer's output is not needed
+      a.z = Z; a.ldz = Cd; a.wpack = img + (long)l * WI;
+      if (gc) { a.gc_tab = gtab + (long)l * B * 2 * Cd; a.gc_ld = 2L * Cd; a.ids = ids; }
+      a.B = B; a.T = T; a.H = H; a.d = x.dw; a.Cr = Cr; a.Cd = Cd;
+      if (int e2 = lbwn_layer_fwd_launch(a, st)) return e2;
+    }
+  }
+  gen_prefill_out_kernel<<<grid((long)B * n), 256, 0, st>>>(codes, (long)ld_codes, (long)n, step, gat<int>(ws, p->oSAMP),
+                                                          gat<float>(ws, p->oWAV), p->max_steps, B, p->Q);
+  LBWN_CHECK_LAUNCH();
+  // last: a call that failed above leaves the counters where the rings' owners expect them
+  unsigned long long* g = gat<unsigned long long>(ws, p->oGRAN);
+  gen_prefill_finish_kernel<<<1, 256, 0, st>>>(codes, (long)ld_codes, (long)n, code, step,
+                                               reinterpret_cast<long long*>(g + p->n_gran_core), p->pgroups, B, p->Q);
+  LBWN_CHECK_LAUNCH();
   return 0;
 }

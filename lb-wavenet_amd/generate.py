@@ -7,6 +7,9 @@ librosa (absent here) is replaced by scipy.io.wavfile for reading the teacher wa
 writing 'gen.i<k>.wav' (float32).  The reference hard-codes gc_ids = [5, 6]
 (generate.py:94); --gc-ids overrides, and the list is cycled over the batch.  Archs with local
 conditioning (the reference's generator has none) take their mel from --mel-npy.
+--teacher-prefill (build extension, off by default) runs the teacher's steps as one parallel prefill;
+the written wav then starts with the µ-law-quantised teacher instead of the draws the model made, and
+ignored, during those steps.  Archs with local conditioning do not take it.
 """
 import argparse
 import json
@@ -22,6 +25,10 @@ def get_args(argv=None):
     p = argparse.ArgumentParser(description='WaveNet')
     p.add_argument('--teacher-wav', '-w', type=str,
                    help='Provide a preliminary teacher-forcing vector to prime the generation')
+    p.add_argument('--teacher-prefill', action='store_true',
+                   help='(build extension) run the teacher\'s steps as one parallel prefill instead of '
+                        'one step at a time; the written wav then starts with the mu-law-quantised teacher '
+                        '(without it: with the draws the model made, and ignored, during those steps)')
     p.add_argument('--teacher-start', '-ts', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--teacher-duration', '-td', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--gen-seconds', '-g', type=float, default=5, help='Number of additional seconds to generate')
@@ -116,7 +123,7 @@ def main(argv=None):
     ids = [int(v) for v in args.gc_ids.split(',') if v.strip()]
     gc_ids = [ids[i % len(ids)] for i in range(args.batch_size)] if arch['n_gc_embed'] else None
     print('Starting inference...')
-    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel)
+    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel, prefill=args.teacher_prefill)
     wav_streams = wav_streams.cpu().numpy()
 
     from scipy.io import wavfile

@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the .so: shared HIP runtime)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'liblbwn.so')   # the in-tree build only (tools/with_lib.py loads variants)
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_int, c_int64, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 c_fp = ctypes.c_void_p   # device pointers are passed as integers
@@ -80,6 +80,7 @@ _SIGS = {
     'lbwn_gen_set_mel': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_void_p]),
     'lbwn_gen_run': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_int, c_void_p]),
     'lbwn_gen_is_persistent': (c_int, [c_void_p]),
+    'lbwn_gen_prefill': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_void_p]),
     'lbwn_mulaw_encode': (c_int, [c_fp, c_fp, c_int64, c_int, c_int, c_void_p]),
     'lbwn_mulaw_decode': (c_int, [c_fp, c_fp, c_int64, c_int, c_void_p]),
     'lbwn_gemm_f32': (c_int, [c_fp, c_int64, c_int, c_fp, c_int64, c_int, c_fp, c_int64, c_int, c_int, c_int,

@@ -13,6 +13,10 @@ Local conditioning (keyword-only ``n_lc_in, n_lc_out, lc_upsample``; the referen
 has no LC path): ``init_buffers`` / ``run`` take ``mel`` [B, n_frames, n_lc_in] (or [n_frames,
 n_lc_in], shared by every stream).  Generation step i is training position i-1, so it is
 conditioned on row max(i-1, 0) of the upsampled mel; n_frames·hop rows cover n_frames·hop + 1 steps.
+
+Prompt prefill (archs without LC): ``prefill(codes)`` advances every stream by n known inputs in one
+parallel pass (lbwn_gen_prefill) instead of n steps; ``run(gen_sz, prefill=True)`` primes with the
+teacher vector that way.  The default teacher path is unchanged.
 """
 import ctypes
 import sys
@@ -141,9 +145,48 @@ class WaveNetGen:
                              % (gen_sz, shp[1], shp[1] * self.hop, shp[1] * self.hop + 1))
         return mel
 
-    def init_buffers(self, gc_ids=None, mel=None):
+    def _check_codes(self, codes):
+        """Prompt codes as an integer [batch_sz, n] or [n] (shared by every stream) array/tensor;
+        ValueError on an LC arch, a float dtype, a shape mismatch or n < 1.  No library call."""
+        if self.arch['n_lc_out'] > 0:
+            raise ValueError('prefill: local conditioning is not supported')
+        if not isinstance(codes, torch.Tensor):
+            codes = np.asarray(codes)
+            if codes.dtype.kind not in 'iu':
+                raise ValueError('prefill: codes must be integers, got dtype %s' % codes.dtype)
+        elif codes.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError('prefill: codes must be integers, got dtype %s' % codes.dtype)
+        shp = tuple(codes.shape)
+        if len(shp) not in (1, 2) or (len(shp) == 2 and shp[0] != self.batch_sz):
+            raise ValueError('prefill: codes have shape %s, expected [n] or [%d, n]' % (shp, self.batch_sz))
+        if shp[-1] < 1:
+            raise ValueError('prefill: n must be >= 1')
+        return codes
+
+    def prefill(self, codes):
+        """Advance every stream by the n known inputs ``codes`` (int [n], shared, or [batch_sz, n]) in
+        parallel over the n positions (lbwn_gen_prefill): the state n teacher-forced steps leave,
+        with the prompt itself as samples / wav of those steps.  On the current stream."""
+        codes = self._check_codes(codes)
+        if self._plan is None:
+            raise RuntimeError('prefill: no plan (build_graph and init_buffers first)')
+        if not isinstance(codes, torch.Tensor):
+            codes = torch.from_numpy(np.ascontiguousarray(codes).astype(np.int32))
+        # kept until the next prefill: the launches read it in stream order
+        self._prefill_codes = codes.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(codes.shape[-1])
+        _lib.check(self.lib.lbwn_gen_prefill(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
+                                             self._prefill_codes.data_ptr(), n if codes.dim() == 2 else 0, n,
+                                             _lib.stream_ptr()))
+        return n
+
+    def init_buffers(self, gc_ids=None, mel=None, prefill=False):
         """imodel.init_buffers: zero the lookback/loop buffers, load teacher + GC ids (+ the mel of
-        an LC arch, upsampled once)."""
+        an LC arch, upsampled once).  ``prefill=True`` with a teacher: start without the teacher
+        vector and prefill its µ-law codes instead (at most max_steps of them); returns the number
+        of steps already taken that way (0 otherwise)."""
+        if prefill and self.teacher_mu is not None:
+            self._check_codes(self.teacher_mu)
         mel = self._check_mel(mel)
         if mel is not None:   # frames past the plan's ceil(max_steps / hop) condition no step
             mel = mel[:, :-(-self.max_steps // self.hop)]
@@ -155,7 +198,7 @@ class WaveNetGen:
             if ids.size != self.batch_sz:
                 raise ValueError('gc_ids has %d entries, batch_sz is %d' % (ids.size, self.batch_sz))
             self._gc = torch.as_tensor(ids, device=self.device)
-        t = self.teacher_mu
+        t = None if prefill else self.teacher_mu
         _lib.check(self.lib.lbwn_gen_start(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                            _lib.ptr(self._gc), _lib.ptr(t), 0 if t is None else t.numel(),
                                            self.seed, int(self.pre_bias), _lib.stream_ptr()))
@@ -165,6 +208,9 @@ class WaveNetGen:
             self._mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
             _lib.check(self.lib.lbwn_gen_set_mel(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                                  self._mel.data_ptr(), self._mel.shape[1], _lib.stream_ptr()))
+        if prefill and self.teacher_mu is not None:
+            return self.prefill(self.teacher_mu.reshape(-1)[:self.max_steps])
+        return 0
 
     def _launch(self, n):
         _lib.check(self.lib.lbwn_gen_run(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(), n,
@@ -192,15 +238,17 @@ class WaveNetGen:
         if n_steps - done > 0:
             self._launch(n_steps - done)
 
-    def run(self, gen_sz, gc_ids=None, mel=None):
+    def run(self, gen_sz, gc_ids=None, mel=None, prefill=False):
         """The reference's sess.run(wave_ops) (generate.py:110): generate gen_sz steps from a
         fresh state; the returned waveform holds whole chunks only (imodel.py:256-258).  LC archs:
-        mel must cover the run, gen_sz <= n_frames·hop + 1."""
+        mel must cover the run, gen_sz <= n_frames·hop + 1.  ``prefill=True``: the teacher's steps
+        are prefilled in parallel instead of stepped (the same continuation up to fp32 rounding;
+        the waveform then starts with the µ-law-quantised teacher, not the model's ignored draws)."""
         mel = self._check_mel(mel, int(gen_sz))
         if self._plan is None or self.max_steps < gen_sz:
             self.build_graph(gen_sz)
-        self.init_buffers(gc_ids, mel)
-        self.step(int(gen_sz))
+        done = self.init_buffers(gc_ids, mel, prefill=prefill)
+        self.step(max(int(gen_sz) - done, 0))
         self.check_status()
         n_out = (int(gen_sz) // self.chunk_sz) * self.chunk_sz
         wav = self.tensor('wav').view(self.batch_sz, self.max_steps)[:, :n_out]
