@@ -133,7 +133,11 @@ typedef struct lbwn_gen_plan lbwn_gen_plan;
  * upsample stages, strides >= 1, n_lc_in and n_lc_out multiples of 4; else EINVAL) and carve the
  * upsampled mel, the upsample stages' scratch and a ring of projected per-step LC terms of NC
  * steps (default 64; env LBWN_GEN_LC_CHUNK=<integer 1..4096> at plan creation overrides it,
- * anything else is EINVAL).  NC bounds the ring's size (NC·L·B·256 bytes), not the run length. */
+ * anything else is EINVAL).  NC bounds the ring's size (NC·L·B·256 bytes), not the run length.
+ * LC plans also carve "pfcond", the projected LC terms of one prefill slice for G consecutive layers
+ * (B·T_s·G·2·n_dil floats; G = min(8, L), env LBWN_GEN_PREFILL_LC_GROUP=<integer 1..L> at plan
+ * creation overrides it, anything else is EINVAL; plans without LC do not read it and keep their
+ * workspace size). */
 int lbwn_gen_plan_create(const lbwn_arch* arch, int batch_sz, int64_t max_steps, int64_t max_teacher,
                          lbwn_gen_plan** out);
 void lbwn_gen_plan_destroy(lbwn_gen_plan* plan);
@@ -144,7 +148,10 @@ size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* plan);
  * hand-off timed out); LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
  * ([B][rows][n_lc_out] bytes), of which lbwn_gen_set_mel fills the first B·n_frames·hop rows
  * densely as [B][n_frames·hop][n_lc_out], and "lccond" fp32 [NC][L][B][64] (slot = step mod NC;
- * columns: signal 0..31 | gate 32..63, zero past n_dil). */
+ * columns: signal 0..31 | gate 32..63, zero past n_dil) and "pfcond" fp32 [B·T_s][G·2·n_dil], the
+ * prefill's scratch (row b·T + j of a slice of T positions, layer l0 + g at column g·2·n_dil: signal
+ * n_dil | gate n_dil; what the last projection launch of the last prefill left).  A name the plan
+ * does not have is EINVAL. */
 int lbwn_gen_tensor(const lbwn_gen_plan* plan, const char* name, size_t* offset, size_t* bytes);
 /* Reset the state (zero lookback rings = imodel's zero-initialised buffers, step 0 input =
  * zero vector), load the teacher codes (device int32, may be NULL) and GC ids (device
@@ -190,13 +197,18 @@ int lbwn_gen_is_persistent(const lbwn_gen_plan* plan);
  * splitmix64(seed, stream, t), so lbwn_gen_start without a teacher + prefill(c, n) + run(k) draws at
  * steps n..n+k-1 what lbwn_gen_start(teacher = c, n) + run(n+k) draws there, up to fp32 rounding of
  * the logits (a draw can differ only at a near tie of the CDF).
+ * LC plans (widened after ABI 5 was declared, same ABI: no signature or symbol changed): step t0+j is
+ * conditioned on lc row r(t0+j) of lbwn_gen_set_mel, r(i) = min(max(i-1, 0), n_frames·hop - 1), as
+ * the same step of lbwn_gen_run is; GC and LC terms add.  Per slice and per G layers one launch
+ * projects the slice's lc rows on the f32 matrix cores into "pfcond"; t0 and the loaded row count are
+ * read on the device, so a captured prefill follows a mel loaded later.  Call after lbwn_gen_set_mel.
  * Stream-ordered, no host synchronisation or allocation, graph-capturable (t0 is read on the device);
  * may be called at t0 = 0 or in the middle of a run, any number of times.  The positions are
  * processed in slices of T_s = the largest multiple of 128 with batch_sz*T_s <= 32768 (at least 128;
  * env LBWN_GEN_PREFILL_SLICE=<integer 1..65536> at plan creation overrides it, anything else is
  * EINVAL there); the scratch, carved at plan creation, does not grow with n.
- * EINVAL before any launch: a null argument, n < 1, ld_codes neither 0 nor >= n, an arch with local
- * conditioning, batch_sz*T_s*n_res >= 2^31.  Codes outside [0, n_quant) are the caller's error; they
+ * EINVAL before any launch: a null argument, n < 1, ld_codes neither 0 nor >= n, an LC plan with no
+ * mel loaded since lbwn_gen_start, batch_sz*T_s*n_res >= 2^31.  Codes outside [0, n_quant) are the caller's error; they
  * are clamped into it. */
 int lbwn_gen_prefill(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* codes,
                      int64_t ld_codes, int64_t n, void* stream);

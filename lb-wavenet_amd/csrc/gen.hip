@@ -21,7 +21,9 @@
 // decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).
 // Prompt prefill (lbwn_gen_prefill): n steps with known inputs as a sliced per-layer forward
 // (layer.hip's layer_fwd_kernel) whose D-separation state is the rings; its kernels are at the end
-// of the namespace below, the step kernels know nothing of it.
+// of the namespace below, the step kernels know nothing of it.  LC plans project the slice's lc
+// rows for G layers at a time on the f32 matrix cores (gen_prefill_lcproj_kernel) into the
+// per-row cond term that kernel already takes.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1278,6 +1280,129 @@ __global__ void gen_prefill_gctab_kernel(const float* gc_proj, float* out, long 
   }
 }
 
+// The LC term of one prefill slice for the G consecutive layers l0 .. l0+G-1:
+//   out[m][g·2Cd + o] = Σ_k lc[b][r][k] · [LC_SIGNAL_l | LC_GATE_l][k][o],  l = l0 + g, o < 2Cd,
+// m = b·T + j the row order layer_fwd_kernel reads (cond + m·ldcond), row stride ld, r = r(t0s + j)
+// of gen_lc_proj_kernel from the same two device words.  Exact f32 on the matrix cores
+// (v_mfma_f32_32x32x2_f32): the weights are the row operand (rows = out channel, as layer.hip's
+// accumulators), the gathered lc rows the column operand, k ascending into ONE accumulator per
+// 32 x 32 tile, so each output is the fmaf chain in k order that gen_lc_proj_kernel computes.  A
+// wave owns one tile: 32 positions x the signal or the gate half; the MFMA's dependent-accumulator
+// latency equals its issue interval, so the one chain keeps the pipe full, and the SIMD's second
+// wave (the other half of the same positions) issues while this one waits for its LDS reads.  A
+// lane ends with 4 consecutive out channels of one position per accumulator quad and stores them
+// as one float4 along o.
+// Block = PLC_POS = 128 rows m, 8 waves (signal | gate, 4 waves of 32 positions each).  LDS, both
+// k-major so that every operand read is one conflict-free ds_read_b32 (the two lane halves read
+// rows k = 2s, 2s + 1):
+//   Xs [kt][PLC_POS]  the lc rows of the block's positions, staged once per block while n_lc_out <= PLC_KT
+//   Ws [kt][64]       one layer's [signal 32 | gate 32] columns, zero past n_dil; the next layer's are
+//                     fetched into registers while this layer's MFMAs issue
+// n_lc_out > PLC_KT takes ceil(n_lc_out / PLC_KT) passes per layer into the same accumulators and
+// restages Xs for each.
+constexpr int PLC_POS = 128, PLC_NW = PLC_POS / 32;   // positions per block, waves per tile half (64 positions: 11 % slower)
+constexpr int PLC_THREADS = 128 * PLC_NW, PLC_KW = PLC_THREADS / 64;
+constexpr int PLC_KT = 80;   // Xs + Ws = 60 KB of the 64 KB of static LDS (arch5's n_lc_out: one pass)
+constexpr int PLC_WR = PLC_KT * 64 / PLC_THREADS;   // weight words a thread carries between passes
+static_assert(PLC_KT % 4 == 0 && PLC_WR * PLC_THREADS == PLC_KT * 64 && PLC_KT * (PLC_POS + 64) * 4 <= 65536,
+              "PLC tile");
+
+struct PrefillLC {
+  const float* lc; const float* wsig; const float* wgate; float* out;
+  const long long* step; const int* n_rows;
+  long off, ld;
+  int B, T, Lo, Cd, l0, G, v4;   // v4: n_dil % 4 == 0 and a 16-byte aligned workspace (float4 stores)
+};
+
+// thread (o = tid & 63, k = tid >> 6 + PLC_KW·i): unconditional loads at clamped indices, then selected
+LBWN_DEV void plc_load_w(const PrefillLC& a, int l, int k0, int kt, int tid, float (&wr)[PLC_WR]) {
+  const int o = tid & 63, oc = o & 31;
+  const float* W = (o < 32 ? a.wsig : a.wgate) + ((long)l * a.Lo + k0) * a.Cd + min(oc, a.Cd - 1);
+#pragma unroll
+  for (int i = 0; i < PLC_WR; ++i) {
+    const int k = (tid >> 6) + PLC_KW * i;
+    wr[i] = W[(long)min(k, kt - 1) * a.Cd];
+    if (k >= kt || oc >= a.Cd) wr[i] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(PLC_THREADS) void gen_prefill_lcproj_kernel(PrefillLC a) {
+  __shared__ __attribute__((aligned(16))) float sm[PLC_KT * (PLC_POS + 64)];
+  float* Xs = sm;
+  float* Ws = sm + PLC_KT * PLC_POS;
+  const int tid = threadIdx.x, lane = tid & 63, w = (tid >> 6) % PLC_NW, gate = tid / (64 * PLC_NW);
+  const int pi = lane & 31, h = lane >> 5;
+  const long M = (long)a.B * a.T, m0 = (long)blockIdx.x * PLC_POS;
+  const long long t0s = *a.step + a.off;
+  const int n_rows = max(*a.n_rows, 1);
+  const int npass = (a.Lo + PLC_KT - 1) / PLC_KT, nst = a.G * npass;
+  const long m = m0 + 32 * w + pi;
+  const bool v4 = a.v4 != 0;
+  float wr[PLC_WR];
+  plc_load_w(a, a.l0, 0, min(PLC_KT, a.Lo), tid, wr);
+  floatx16 acc;
+  for (int p = 0; p < nst; ++p) {
+    const int g = p / npass, k0 = (p % npass) * PLC_KT, kt = min(PLC_KT, a.Lo - k0);
+    if (p) __syncthreads();   // the previous pass's LDS reads are done
+    if (p == 0 || npass > 1) {
+      // Xs[k][pos]: lanes along pos (conflict-free stores); a position's row is contiguous in "lc",
+      // and consecutive positions of a stream are consecutive rows except at the two clamps
+      const int kt4 = kt >> 2;   // Lo is a multiple of 4
+      for (int e = tid; e < PLC_POS * kt4; e += PLC_THREADS) {
+        const int pos = e & (PLC_POS - 1), k = 4 * (e / PLC_POS);
+        const long mm = min(m0 + pos, M - 1);
+        const long b = mm / a.T;
+        const long long r = min(max(t0s + (mm - b * a.T) - 1, 0LL), (long long)n_rows - 1);
+        const floatx4 x = *(const floatx4*)(a.lc + ((long)b * n_rows + r) * a.Lo + k0 + k);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Xs[(k + i) * PLC_POS + pos] = x[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < PLC_WR; ++i) Ws[((tid >> 6) + PLC_KW * i) * 64 + (tid & 63)] = wr[i];
+    __syncthreads();
+    if (p + 1 < nst) {   // in flight during the MFMAs below
+      const int k1 = ((p + 1) % npass) * PLC_KT;
+      plc_load_w(a, a.l0 + (p + 1) / npass, k1, min(PLC_KT, a.Lo - k1), tid, wr);
+    }
+    if (k0 == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    }
+    const float* xk = Xs + h * PLC_POS + 32 * w + pi;
+    const float* wk = Ws + h * 64 + 32 * gate + pi;
+    // lane half h supplies k = s + h.  Four MFMAs per group of LDS reads: one read latency per 256
+    // MFMA cycles instead of one per 64 (kt is a multiple of 4: a last group of two)
+    int s = 0;
+    for (; s + 8 <= kt; s += 8) {
+      float x[4], wv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { x[i] = xk[(s + 2 * i) * PLC_POS]; wv[i] = wk[(s + 2 * i) * 64]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc = mfma32(wv[i], x[i], acc);
+    }
+    if (s < kt) {
+      const float x0 = xk[s * PLC_POS], w0 = wk[s * 64], x1 = xk[(s + 2) * PLC_POS], w1 = wk[(s + 2) * 64];
+      acc = mfma32(w0, x0, acc);
+      acc = mfma32(w1, x1, acc);
+    }
+    if (k0 + kt == a.Lo && m < M) {
+      float* row = a.out + m * a.ld + (long)g * 2 * a.Cd + gate * a.Cd;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int o = 8 * q + 4 * h;   // acc_row(4q, h): this lane's 4 consecutive out channels
+        if (v4) {
+          if (o < a.Cd) *(floatx4*)(row + o) = floatx4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (o + i < a.Cd) row[o + i] = acc[4 * q + i];
+        }
+      }
+    }
+  }
+}
+
 // outputs of the prefilled steps: samples = the prompt, wav = its µ-law decode (the counter is only read)
 __global__ void gen_prefill_out_kernel(const int* codes, long ld_codes, long n, const long long* step, int* samples,
                                        float* wav, long long max_steps, int B, int Q) {
@@ -1338,14 +1463,16 @@ struct lbwn_gen_plan {
   // prefill (lbwn_gen_prefill): slice length, halo, and the scratch -- two halo
   // buffers [B][pfH + pfT][Cr], z [B·pfT][Cd], the L packed layer images, the per-stream GC table
   // [L][B][2·Cd] and ids [B][pfT]
-  int pfT = 0, pfH = 0;
-  size_t oPFX[2] = {0, 0}, oPFZ = 0, oPFIMG = 0, oPFGC = 0, oPFIDS = 0;
+  // LC plans: the projected LC terms of one slice for pfG consecutive layers, "pfcond" [B·pfT][pfG·2·Cd]
+  int pfT = 0, pfH = 0, pfG = 0;
+  size_t oPFX[2] = {0, 0}, oPFZ = 0, oPFIMG = 0, oPFGC = 0, oPFIDS = 0, oPFCOND = 0;
 };
 
 constexpr int G_LC_CHUNK = 64;         // default NC (steps per projection launch / persistent sub-run)
 constexpr int G_LC_CHUNK_MAX = 4096;
 constexpr int G_PF_ROWS = 32768;       // default prefill slice: B·T_s rows per layer launch (the C2 launch size)
 constexpr int G_PF_SLICE_MAX = 65536;
+constexpr int G_PF_LC_GROUP = 8;       // default layers per prefill projection launch
 
 // the per-step GEMM form: large B, shapes the split GEMM takes (N % 4, K % 4, row strides)
 static bool gemm_form_ok(const lbwn_gen_plan* p) {
@@ -1367,6 +1494,8 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   // local conditioning: the training plan's limits (lbwn_plan_create)
   long long hop = 1;
   int lc_chunk = G_LC_CHUNK;
+  const int n_layers = a->n_blocks * a->n_block_layers;
+  int pf_group = std::min(G_PF_LC_GROUP, n_layers);
   if (a->n_lc_out > 0) {
     LBWN_REQUIRE(a->n_lc_upsample >= 1 && a->n_lc_upsample <= 8, "gen: LC needs 1..8 upsample stages");
     for (int i = 0; i < a->n_lc_upsample; ++i) {
@@ -1386,6 +1515,14 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     }
     LBWN_REQUIRE((long long)lc_chunk * B / LCP_ROWS < 65535, "gen: LBWN_GEN_LC_CHUNK %d x batch_sz %d is too large",
                  lc_chunk, B);   // the projection's grid: one block row per LCP_ROWS (step, stream) pairs
+    if (const char* ge = getenv("LBWN_GEN_PREFILL_LC_GROUP")) {
+      char* end = nullptr;
+      const long v = strtol(ge, &end, 10);
+      LBWN_REQUIRE(end != ge && *end == 0 && v >= 1 && v <= n_layers,
+                   "gen: LBWN_GEN_PREFILL_LC_GROUP must be an integer in 1..%d, the number of layers (got '%s')",
+                   n_layers, ge);
+      pf_group = (int)v;
+    }
   }
   // prefill slice length: the largest multiple of 128 with B·T_s <= G_PF_ROWS, at least 128
   int pf_slice = std::max(LBWN_LAYER_POS, G_PF_ROWS / B / LBWN_LAYER_POS * LBWN_LAYER_POS);
@@ -1469,8 +1606,8 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     p->oLCC = gcarve(cur, 4 * (size_t)p->NC * p->L * B * 64);
     p->up_fused = lbwn_lc_up_fused_ok(p->nup, p->up, p->Li, p->Lo) != 0;
   }
-  {   // prefill scratch: independent of the prompt length (LC plans, which prefill refuses, carve it
-      // too: a plan's workspace is that of the same arch without LC plus the LC tensors)
+  {   // prefill scratch: independent of the prompt length (a plan's workspace is that of the same
+      // arch without LC plus the LC tensors, "pfcond" the last of them)
     p->pfT = pf_slice;
     p->pfH = 1 << (p->nbl - 1);
     for (int i = 0; i < 2; ++i) p->oPFX[i] = gcarve(cur, 4 * (size_t)B * ((size_t)p->pfH + p->pfT) * p->Cr);
@@ -1479,6 +1616,10 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     if (a->n_gc_embed > 0) {
       p->oPFGC = gcarve(cur, 4 * (size_t)p->L * B * 2 * p->Cd);
       p->oPFIDS = gcarve(cur, 4 * (size_t)B * p->pfT);
+    }
+    if (p->Lo > 0) {
+      p->pfG = pf_group;
+      p->oPFCOND = gcarve(cur, 4 * (size_t)B * p->pfT * p->pfG * 2 * p->Cd);
     }
   }
   p->total = cur;
@@ -1502,6 +1643,7 @@ extern "C" int lbwn_gen_tensor(const lbwn_gen_plan* p, const char* name, size_t*
   else if (!strcmp(name, "teacher")) { *off = p->oTEACH; *bytes = 4 * (size_t)std::max<long long>(1, p->n_teacher); }
   else if (p->Lo > 0 && !strcmp(name, "lc")) { *off = p->oLC; *bytes = 4 * B * (size_t)p->lc_rows * p->Lo; }
   else if (p->Lo > 0 && !strcmp(name, "lccond")) { *off = p->oLCC; *bytes = 4 * (size_t)p->NC * p->L * B * 64; }
+  else if (p->Lo > 0 && !strcmp(name, "pfcond")) { *off = p->oPFCOND; *bytes = 4 * B * (size_t)p->pfT * p->pfG * 2 * p->Cd; }
   else LBWN_REQUIRE(false, "gen_tensor: unknown tensor '%s'", name);
   return 0;
 }
@@ -1748,7 +1890,9 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
   LBWN_REQUIRE(n >= 1, "prefill: n must be >= 1 (got %lld)", (long long)n);
   LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "prefill: ld_codes %lld must be 0 (one shared vector) or >= n = %lld",
                (long long)ld_codes, (long long)n);
-  LBWN_REQUIRE(p->Lo == 0, "prefill: local conditioning is not supported");
+  LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded,
+               "prefill: local conditioning is not supported before lbwn_gen_set_mel (no mel loaded)");
+  LBWN_REQUIRE(p->Lo == 0 || (P->lc_sig && P->lc_gate), "prefill: LC_SIGNAL/LC_GATE pointers are null");
   LBWN_REQUIRE((long long)p->B * p->pfT * p->Cr < (1LL << 31), "prefill: batch_sz %d x slice %d x n_res %d >= 2^31",
                p->B, p->pfT, p->Cr);
   hipStream_t st = (hipStream_t)stream;
@@ -1763,6 +1907,8 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
   float* gtab = gc ? gat<float>(ws, p->oPFGC) : nullptr;
   int* ids = gc ? gat<int>(ws, p->oPFIDS) : nullptr;
   const bool bias = p->pre_bias && P->pre_b;
+  float* pfcond = p->Lo > 0 ? gat<float>(ws, p->oPFCOND) : nullptr;
+  const long ldcond = (long)p->pfG * 2 * Cd;
   // float4 rows: the buffers and rings are 256-B carved and every ring offset is a multiple of Cr
   const bool xv4 = Cr % 4 == 0 && (((uintptr_t)ws) & 15) == 0;
   const bool ev4 = xv4 && (((uintptr_t)P->pre) & 15) == 0 && (!bias || (((uintptr_t)P->pre_b) & 15) == 0);
@@ -1805,11 +1951,22 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
       else gen_prefill_xfer_kernel<false><<<grid(items * Cr), 256, 0, st>>>(x);
       LBWN_CHECK_LAUNCH();
       if (l < 0) continue;
+      if (p->Lo > 0 && l % p->pfG == 0) {   // the LC terms of layers l .. l + G - 1 for this slice
+        PrefillLC c;
+        c.lc = gat<float>(ws, p->oLC); c.wsig = P->lc_sig; c.wgate = P->lc_gate; c.out = pfcond;
+        c.step = step; c.n_rows = gat<int>(ws, p->oSTEP + 12);
+        c.off = (long)off; c.ld = ldcond;
+        c.B = B; c.T = T; c.Lo = p->Lo; c.Cd = Cd; c.l0 = l; c.G = std::min(p->pfG, L - l);
+        c.v4 = Cd % 4 == 0 && (((uintptr_t)ws) & 15) == 0;
+        gen_prefill_lcproj_kernel<<<(unsigned)(((long)B * T + PLC_POS - 1) / PLC_POS), PLC_THREADS, 0, st>>>(c);
+        LBWN_CHECK_LAUNCH();
+      }
       lbwn_layer_args a;
       memset(&a, 0, sizeof(a));
       a.x_in = X[l & 1]; a.x_out = l + 1 < L ? X[(l + 1) & 1] : nullptr;   // the last layer's output is not needed
       a.z = Z; a.ldz = Cd; a.wpack = img + (long)l * WI;
       if (gc) { a.gc_tab = gtab + (long)l * B * 2 * Cd; a.gc_ld = 2L * Cd; a.ids = ids; }
+      if (p->Lo > 0) { a.cond = pfcond + (long)(l % p->pfG) * 2 * Cd; a.ldcond = ldcond; }   // GC and LC add, as in training
       a.B = B; a.T = T; a.H = H; a.d = x.dw; a.Cr = Cr; a.Cd = Cd;
       if (int e2 = lbwn_layer_fwd_launch(a, st)) return e2;
     }

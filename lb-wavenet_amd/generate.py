@@ -9,7 +9,8 @@ writing 'gen.i<k>.wav' (float32).  The reference hard-codes gc_ids = [5, 6]
 conditioning (the reference's generator has none) take their mel from --mel-npy.
 --teacher-prefill (build extension, off by default) runs the teacher's steps as one parallel prefill;
 the written wav then starts with the µ-law-quantised teacher instead of the draws the model made, and
-ignored, during those steps.  Archs with local conditioning do not take it.
+ignored, during those steps.  With --mel-npy the prefilled steps are conditioned on the mel like the
+sequential ones (upsampled row i-1 for step i).
 """
 import argparse
 import json

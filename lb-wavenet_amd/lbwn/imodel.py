@@ -14,9 +14,11 @@ has no LC path): ``init_buffers`` / ``run`` take ``mel`` [B, n_frames, n_lc_in] 
 n_lc_in], shared by every stream).  Generation step i is training position i-1, so it is
 conditioned on row max(i-1, 0) of the upsampled mel; n_frames·hop rows cover n_frames·hop + 1 steps.
 
-Prompt prefill (archs without LC): ``prefill(codes)`` advances every stream by n known inputs in one
-parallel pass (lbwn_gen_prefill) instead of n steps; ``run(gen_sz, prefill=True)`` primes with the
-teacher vector that way.  The default teacher path is unchanged.
+Prompt prefill: ``prefill(codes)`` advances every stream by n known inputs in one parallel pass
+(lbwn_gen_prefill) instead of n steps; ``run(gen_sz, prefill=True)`` primes with the teacher vector
+that way.  On an LC arch the prefilled steps are conditioned on the loaded mel like any other step
+(``init_buffers(mel=...)`` first, or ``run(gen_sz, mel=..., prefill=True)``).  The default teacher
+path is unchanged.
 """
 import ctypes
 import sys
@@ -58,6 +60,7 @@ class WaveNetGen:
         self._plan = None
         self._ws = None
         self._graph = None
+        self._mel = None      # the mel loaded by the last init_buffers (None: none since lbwn_gen_start)
 
     # ---- parameters -------------------------------------------------------------------------
     def load_params(self, src):
@@ -145,11 +148,13 @@ class WaveNetGen:
                              % (gen_sz, shp[1], shp[1] * self.hop, shp[1] * self.hop + 1))
         return mel
 
-    def _check_codes(self, codes):
+    def _check_codes(self, codes, mel_coming=False):
         """Prompt codes as an integer [batch_sz, n] or [n] (shared by every stream) array/tensor;
-        ValueError on an LC arch, a float dtype, a shape mismatch or n < 1.  No library call."""
-        if self.arch['n_lc_out'] > 0:
-            raise ValueError('prefill: local conditioning is not supported')
+        ValueError on an LC arch with no mel loaded (and none being loaded by the same
+        init_buffers call: mel_coming), a float dtype, a shape mismatch or n < 1.  No library call."""
+        if self.arch['n_lc_out'] > 0 and self._mel is None and not mel_coming:
+            raise ValueError('prefill: local conditioning is not supported before a mel is loaded '
+                             '(init_buffers(mel=...) first)')
         if not isinstance(codes, torch.Tensor):
             codes = np.asarray(codes)
             if codes.dtype.kind not in 'iu':
@@ -184,9 +189,10 @@ class WaveNetGen:
         """imodel.init_buffers: zero the lookback/loop buffers, load teacher + GC ids (+ the mel of
         an LC arch, upsampled once).  ``prefill=True`` with a teacher: start without the teacher
         vector and prefill its µ-law codes instead (at most max_steps of them); returns the number
-        of steps already taken that way (0 otherwise)."""
+        of steps already taken that way (0 otherwise); on an LC arch the prefilled steps are
+        conditioned on the mel this call loads."""
         if prefill and self.teacher_mu is not None:
-            self._check_codes(self.teacher_mu)
+            self._check_codes(self.teacher_mu, mel_coming=mel is not None)
         mel = self._check_mel(mel)
         if mel is not None:   # frames past the plan's ceil(max_steps / hop) condition no step
             mel = mel[:, :-(-self.max_steps // self.hop)]
@@ -202,6 +208,7 @@ class WaveNetGen:
         _lib.check(self.lib.lbwn_gen_start(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                            _lib.ptr(self._gc), _lib.ptr(t), 0 if t is None else t.numel(),
                                            self.seed, int(self.pre_bias), _lib.stream_ptr()))
+        self._mel = None      # lbwn_gen_start clears the loaded mel
         if mel is not None:
             if not isinstance(mel, torch.Tensor):
                 mel = torch.from_numpy(np.ascontiguousarray(mel, np.float32))

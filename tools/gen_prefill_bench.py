@@ -4,7 +4,9 @@ shared prompt; each is timed with device events around the call alone (the reset
 one warm-up, as the median of --reps runs.  Writes a markdown table (both times and the ratio) to
 --out; with --kernel-stats (the *kernel_stats.csv of a `rocprofv3 --kernel-trace --stats` run of this
 tool with --prefill-only) the prefill's kernel time is split into the layer launches and the
-embed / copy / finish kernels.  No test asserts these times."""
+embed / copy / finish kernels (LC archs: and the LC projection launches).  Archs with local
+conditioning get a random mel covering the prompt; --strip-lc runs the same arch without
+its n_lc_* keys, as tools/arch5_nogc.json does for GC.  No test asserts these times."""
 import argparse
 import csv
 import os
@@ -22,18 +24,21 @@ ap.add_argument('--reps', type=int, default=5)
 ap.add_argument('--chunk', type=int, default=1000, help='graph-replay chunk of the sequential path')
 ap.add_argument('--prefill-only', action='store_true', help='no sequential runs (for a profiler run)')
 ap.add_argument('--kernel-stats', default=None, metavar='CSV')
+ap.add_argument('--strip-lc', action='store_true', help='run the arch without its local conditioning')
 ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r08_gen_prefill.md'))
 a = ap.parse_args()
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from lbwn.arch import load_arch  # noqa: E402
+from lbwn.arch import load_arch, mel_hop_sz, normalize_arch  # noqa: E402
 from lbwn.imodel import WaveNetGen  # noqa: E402
 from lbwn.tmodel import WaveNetTrain  # noqa: E402
 
 assert torch.cuda.is_available(), 'needs an MI355X'
 arch = load_arch(a.arch)
-assert arch['n_lc_out'] == 0, 'prefill has no local conditioning'
+if a.strip_lc:
+    arch = normalize_arch({k: v for k, v in arch.items() if k not in ('n_lc_in', 'n_lc_out', 'lc_upsample')})
+lc = arch['n_lc_out'] > 0
 net = WaveNetTrain(**arch, batch_sz=1, l2_factor=0.0, print_interval=0, seed=0)
 
 
@@ -59,24 +64,30 @@ for B in a.batch:
         codes = torch.as_tensor(np.random.default_rng(n).integers(0, arch['n_quant'], n).astype(np.int32), device='cuda')
         g = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                        arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
-                       B, a.chunk, None, seed=1)
+                       B, a.chunk, None, seed=1, n_lc_in=arch['n_lc_in'], n_lc_out=arch['n_lc_out'],
+                       lc_upsample=arch['lc_upsample'])
         g.load_params(net)
         g.build_graph(n)
         gc = list(range(1, B + 1)) if arch['n_gc_embed'] else None
-        pf = timed(lambda: g.prefill(codes), lambda: g.init_buffers(gc))
+        mel = None
+        if lc:   # the rows of steps 0 .. n-1
+            mel = torch.randn(B, -(-n // mel_hop_sz(arch)), arch['n_lc_in'], generator=torch.Generator().manual_seed(n))
+            mel = mel.to('cuda')
+        pf = timed(lambda: g.prefill(codes), lambda: g.init_buffers(gc, mel=mel))
         assert int(g.tensor('step', torch.int64).item()) == n
         seq = None
         if not a.prefill_only:
             g.teacher_mu = codes
             g.build_graph(n)        # a plan with room for the teacher vector
-            seq = timed(lambda: g.step(n), lambda: g.init_buffers(gc))
+            seq = timed(lambda: g.step(n), lambda: g.init_buffers(gc, mel=mel))
             assert int(g.tensor('step', torch.int64).item()) == n
             g.check_status()
         rows.append((B, n, g.persistent, pf, seq))
         print('B=%d n=%d prefill %.3f ms%s' % (B, n, pf[0], '' if seq is None else
                                               ', sequential %.1f ms, ratio %.0fx' % (seq[0], seq[0] / pf[0])), flush=True)
 
-out = ['# Prompt prefill against the sequential teacher path (%s)' % os.path.basename(a.arch), '',
+out = ['# Prompt prefill against the sequential teacher path (%s%s)' % (
+    os.path.basename(a.arch), ', local conditioning stripped' if a.strip_lc else ''), '',
        'Device events around the call, one warm-up, median of %d (min .. max); the sequential path steps' % a.reps,
        'through graph replays of %d steps.' % a.chunk, '',
        '| B | prompt n | form | prefill ms | sequential ms | ratio | prefill us per code |', '|---:|---:|---|---:|---:|---:|---:|']
@@ -91,6 +102,7 @@ if a.kernel_stats:
     for r in ks:
         nm = r['Name']
         key = ('layer launches (layer_fwd_kernel)' if 'layer_fwd_kernel' in nm else
+               'LC projection (gen_prefill_lcproj_kernel)' if 'gen_prefill_lcproj' in nm else
                'ring <-> halo copies (gen_prefill_xfer_kernel)' if 'gen_prefill_xfer' in nm else
                'embed (gen_prefill_embed_kernel)' if 'gen_prefill_embed' in nm else
                'pack / GC table / outputs / finish' if ('gen_prefill' in nm or 'pack_layers_kernel' in nm) else None)
