@@ -212,6 +212,32 @@ int lbwn_gen_is_persistent(const lbwn_gen_plan* plan);
  * are clamped into it. */
 int lbwn_gen_prefill(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* codes,
                      int64_t ld_codes, int64_t n, void* stream);
+/* Temperature, top-k and nucleus (top-p) filtering of the draw (added after ABI 5 was declared, same
+ * ABI: two symbols added, none altered -- the convention of the LC widening of lbwn_gen_prefill).
+ * With l a stream's logits at a step (the values "logits" holds, which stays raw):
+ *  1. top_k (0 = off): keep the codes whose logit is >= the k-th largest logit; ties with the k-th are
+ *     kept; top_k >= n_quant is normalised to 0.
+ *  2. temperature T (finite, > 0; 1 = off): e_c = exp((l_c - max l) / T) for kept codes, 0 otherwise.
+ *     Greedy decoding is top_k = 1.
+ *  3. top_p (0 < p <= 1; 1 = off), applied after top-k: order the kept codes by e, descending; keep the
+ *     shortest prefix whose mass is >= p·Σe, plus every code whose e equals that prefix's last member;
+ *     all others get e = 0.
+ *  4. The draw is lbwn_gen_start's, over the surviving e in code order: the first code with
+ *     cumsum(e) > u·Σe, u = splitmix64(seed, stream, step) >> 40 / 2^24.  The µ-law decode, "samples",
+ *     "wav", the pending input and the teacher override are unchanged: a teacher-forced step stores the
+ *     filtered draw and feeds the teacher's code.  lbwn_gen_prefill draws nothing and is not affected.
+ * Plan host state like the seed: (1, 0, 1) at plan creation, kept across lbwn_gen_start, read by each
+ * later lbwn_gen_run when it launches -- so a captured graph bakes in the values of its capture; capture
+ * again after changing them.  No launch, no device access, no workspace: the workspace size does not
+ * depend on it.  The neutral triple (1, 0, 1) launches the unfiltered kernels: draws are bitwise what
+ * they were without this call.  Otherwise the same launches run a filtered form of the draw (wave-level
+ * bisection on the logit and e bit patterns, <= 32 + 30 short rounds per draw).
+ * EINVAL, naming the argument, and nothing changed: plan NULL, temperature not finite or <= 0,
+ * top_k < 0, top_p NaN, <= 0 or > 1. */
+int lbwn_gen_set_sampling(lbwn_gen_plan* plan, float temperature, int top_k, float top_p);
+/* The plan's normalised values (a top_k >= n_quant reads back as 0); NULL outputs are skipped.
+ * EINVAL when plan is NULL. */
+int lbwn_gen_get_sampling(const lbwn_gen_plan* plan, float* temperature, int* top_k, float* top_p);
 
 /* ---- fine-grained kernels (parity tests, custom drivers) ------------------------------ */
 /* ops.mu_encode_np (ops.py:23-28, tf32=0, float64 math) / ops.mu_encode (ops.py:4-9, tf32=1) */

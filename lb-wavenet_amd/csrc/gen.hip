@@ -18,7 +18,9 @@
 // the mel once, gen_lc_proj_kernel projects it for the next <= NC steps into a cond ring, and the
 // step kernels' loaders DMA that step's row into the fourth bias row of each layer's LDS slot.
 // Both draw with the same wave-level inverse-CDF code: u = hash(seed, stream, step), µ-law
-// decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).
+// decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).  A sampling triple other
+// than (1, 0, 1) (lbwn_gen_set_sampling: temperature, top_k, top_p) selects the FILT instantiations,
+// whose draw filters the codes first (draw_core_filt); the neutral triple runs the plain ones.
 // Prompt prefill (lbwn_gen_prefill): n steps with known inputs as a sliced per-layer forward
 // (layer.hip's layer_fwd_kernel) whose D-separation state is the rings; its kernels are at the end
 // of the namespace below, the step kernels know nothing of it.  LC plans project the slice's lc
@@ -434,6 +436,7 @@ struct DrawK {
   int Q, B;
   float* logits; int* samples; float* wav; long long max_steps;
   const int* teacher; long long n_teacher; unsigned long long seed; int* code;
+  float temperature; int top_k; float top_p;   // lbwn_gen_set_sampling; read by the FILT forms only
 };
 
 // wave-wide max / min / inclusive scan on DPP (row ops + row_bcast, GFX9): one VALU latency
@@ -469,6 +472,19 @@ LBWN_DEV float wave_scan(float x) {
   x += __int_as_float(dpp_i<0x142, 0xA>(__float_as_int(x)));
   x += __int_as_float(dpp_i<0x143, 0xC>(__float_as_int(x)));
   return x;
+}
+// wave-wide sum, the same value on every lane (each step adds a lane's partner, so both sides of a
+// pair form the same sum): the filtered draw's masses
+LBWN_DEV float wave_sum(float v) {
+  v += __int_as_float(dpp_i<0xB1>(__float_as_int(v)));
+  v += __int_as_float(dpp_i<0x4E>(__float_as_int(v)));
+  v += __int_as_float(dpp_i<0x141>(__float_as_int(v)));
+  v += __int_as_float(dpp_i<0x140>(__float_as_int(v)));
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+  const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+  const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+  return (r0 + r1) + (r2 + r3);
 }
 
 LBWN_DEV uint64_t splitmix(uint64_t seed, uint64_t stream, uint64_t step) {
@@ -550,8 +566,107 @@ LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool 
   return next;
 }
 
-// per-step path: logits from the post2 GEMV's K-slice partials, Σ in slice order + bias
+// The filtered draw (lbwn_gen_set_sampling: temperature T, top_k, top_p), same
+// contract as draw_core: wave-level only, no LDS, and every step a function of the logits alone, so
+// the four compute waves of a chain block reach the same code.  Both filters are thresholds on one
+// ordering, found by bisection on integer bit patterns:
+//   top_k  key = the logit's bits made order-preserving (slots past Q get key 0, below every real
+//          key); K = the largest key with #{key >= K} >= k, i.e. the k-th largest key, built bit by
+//          bit from the top: 32 rounds of MP compares, the count = popcount of the wave's ballot
+//          (scalar, no cross-lane traffic).  Kept: key >= K, ties with the k-th included.
+//   e      exp((l - max) / T) on the kept codes, 0 elsewhere.
+//   top_p  e >= 0, so its bits are monotone in e; th = the largest pattern with Σ{e : bits(e) >= th}
+//          >= p·Σe, i.e. the smallest e of the shortest descending prefix that reaches p: 30 rounds
+//          (e <= 1 < 2^30 as bits) of a masked wave sum.  Kept: bits(e) >= th, its ties included.
+// The inverse-CDF walk is draw_core's over the surviving e; its rounding fallbacks (no lane or no
+// code crossing the target) take the last SURVIVING code, never a filtered one.
 template <int MP>
+LBWN_DEV int draw_core_filt(float (&v)[MP], const DrawK& a, int b, long long t, bool write, bool decode = true) {
+  const int lane = threadIdx.x & 63, Q = a.Q;
+  const int per = (Q + 63) >> 6, c0 = lane * per;
+  float mx = -INFINITY;
+  unsigned key[MP];
+#pragma unroll
+  for (int j = 0; j < MP; ++j) {
+    const bool ok = j < per && c0 + j < Q;
+    if (ok) mx = fmaxf(mx, v[j]);
+    if (ok && write) a.logits[(long)b * Q + c0 + j] = v[j];
+    const unsigned bits = __float_as_uint(v[j] + 0.f);   // -0 -> +0: equal logits, equal keys
+    key[j] = ok ? (bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u)) : 0u;
+  }
+  mx = wave_max(mx);
+  unsigned K = 1u;   // top_k off: every real key
+  if (a.top_k > 0) {
+    K = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned tr = K | (1u << bit);
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < MP; ++j) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(key[j] >= tr));
+      if (cnt >= a.top_k) K = tr;
+    }
+    K = max(K, 1u);
+  }
+  const float T = a.temperature;
+  float e[MP], loc = 0.f;
+#pragma unroll
+  for (int j = 0; j < MP; ++j) {
+    e[j] = key[j] >= K ? expf((v[j] - mx) / T) : 0.f;
+    loc += e[j];
+  }
+  if (a.top_p < 1.f) {
+    const float goal = a.top_p * wave_sum(loc);
+    unsigned th = 0u;
+    for (int bit = 29; bit >= 0; --bit) {
+      const unsigned tr = th | (1u << bit);
+      float m = 0.f;
+#pragma unroll
+      for (int j = 0; j < MP; ++j) m += __float_as_uint(e[j]) >= tr ? e[j] : 0.f;
+      if (wave_sum(m) >= goal) th = tr;
+    }
+    loc = 0.f;
+#pragma unroll
+    for (int j = 0; j < MP; ++j) {
+      if (__float_as_uint(e[j]) < th) e[j] = 0.f;
+      loc += e[j];
+    }
+  }
+  const float incl = wave_scan(loc);
+  const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
+  const float excl = incl - loc;
+  const uint64_t h = splitmix(a.seed, (uint64_t)b, (uint64_t)t);
+  const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
+  const float target = u * total;
+  int found = Q, lastc = -1;   // lastc: this lane's last surviving code (e > 0 only on codes < Q)
+#pragma unroll
+  for (int j = 0; j < MP; ++j)
+    if (e[j] > 0.f) lastc = c0 + j;
+  if (loc > 0.f && target < incl) {   // the first such lane holds the crossing point (wave_min below)
+    float run = excl;
+#pragma unroll
+    for (int j = 0; j < MP; ++j) {
+      if (e[j] > 0.f && found == Q) {
+        run += e[j];
+        if (run > target) found = c0 + j;
+      }
+    }
+    if (found == Q) found = lastc;
+  }
+  found = wave_min(found);
+  if (found >= Q) found = -wave_min(-lastc);   // target rounded up to the total: the last survivor
+  const int next = (t < a.n_teacher) ? a.teacher[t] : found;   // imodel.py:260-269
+  if (write && lane == 0) {
+    if (t < a.max_steps) {
+      a.samples[(long)b * a.max_steps + t] = found;
+      if (decode) a.wav[(long)b * a.max_steps + t] = mu_decode_q(found, Q);
+    }
+    a.code[b] = next;
+  }
+  return next;
+}
+
+// per-step path: logits from the post2 GEMV's K-slice partials, Σ in slice order + bias
+template <int MP, bool FILT = false>
 LBWN_DEV int draw_wave(const DrawK& a, int b, long long t, bool write) {
   const int lane = threadIdx.x & 63, Q = a.Q;
   const int per = (Q + 63) >> 6, c0 = lane * per;
@@ -578,7 +693,8 @@ LBWN_DEV int draw_wave(const DrawK& a, int b, long long t, bool write) {
 #pragma unroll
     for (int j = 0; j < MP; ++j) v[j] += bv[j];
   }
-  return draw_core<MP>(v, a, b, t, write);
+  if constexpr (FILT) return draw_core_filt<MP>(v, a, b, t, write);
+  else return draw_core<MP>(v, a, b, t, write);
 }
 
 // the per-step path's sampler: one wave per stream; the step counter was advanced by this
@@ -587,6 +703,12 @@ __global__ __launch_bounds__(64) void gen_sample_kernel(DrawK a, const long long
   const long long t = *step - 1;
   if (a.Q > 256) draw_wave<8>(a, blockIdx.x, t, true);
   else draw_wave<4>(a, blockIdx.x, t, true);
+}
+// the same with the filtered draw (a second kernel, so the default sampler's code is untouched)
+__global__ __launch_bounds__(64) void gen_sample_filt_kernel(DrawK a, const long long* step) {
+  const long long t = *step - 1;
+  if (a.Q > 256) draw_wave<8, true>(a, blockIdx.x, t, true);
+  else draw_wave<4, true>(a, blockIdx.x, t, true);
 }
 
 #ifndef LBWN_GEN_SUBSTAMPS
@@ -682,7 +804,7 @@ LBWN_DEV void dma4_sc1(const float* src, float* lds_dst) {
 }
 
 
-template <bool LC>
+template <bool LC, bool FILT>
 LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* stepc, long long* trace) {
   float* RING = sm;                  // [G_NS][G_SLOT]
   float* XP = sm + G_NS * G_SLOT;    // [L][32] dilated taps of this step
@@ -822,7 +944,8 @@ LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* step
         lv[j] = DL[cc] + DL[256 + cc];
         if (a.draw.bias) lv[j] += bq[j];
       }
-      code = draw_core<4>(lv, a.draw, b, t - 1, w == 0, false);
+      if constexpr (FILT) code = draw_core_filt<4>(lv, a.draw, b, t - 1, w == 0, false);
+      else code = draw_core<4>(lv, a.draw, b, t - 1, w == 0, false);
       if (s == n) {
         if (tr) tr[6] = wall_clock64();
         break;
@@ -1074,14 +1197,15 @@ LBWN_DEV void persist_head(const PersistK& a, int m, float* sm, int b0, int B, l
   }
 }
 
-template <bool LC>
+// FILT: the chain blocks draw with draw_core_filt (the head blocks are the same code either way)
+template <bool LC, bool FILT>
 __global__ __launch_bounds__(512) void gen_persist_kernel(PersistK a) {
   __shared__ __attribute__((aligned(16))) float sm[G_LDS];
   const int per = a.Bg + P_NH, g = blockIdx.x / per, r = blockIdx.x % per;
   const int b0 = g * a.Bg, Bg = min(a.Bg, a.B - b0);
   long long* stepc = g ? a.gstep + (g - 1) : a.step;
   long long* trace = g ? nullptr : a.trace;
-  if (r < Bg) persist_chain<LC>(a, sm, b0 + r, stepc, trace);
+  if (r < Bg) persist_chain<LC, FILT>(a, sm, b0 + r, stepc, trace);
   else if (r >= a.Bg) persist_head(a, r - a.Bg, sm, b0, Bg, stepc, trace);
   // (a ragged last group leaves chain slots r in [Bg, a.Bg) idle)
 }
@@ -1453,6 +1577,10 @@ struct lbwn_gen_plan {
   long long n_teacher, max_teacher;
   unsigned long long seed;
   int pre_bias;
+  // the draw's filters (lbwn_gen_set_sampling), normalised; host state like the seed, read by each
+  // lbwn_gen_run at launch.  Neutral (1, 0, 1) launches the unfiltered kernels.
+  float temperature = 1.f, top_p = 1.f;
+  int top_k = 0;
   // local conditioning (Lo = 0: none): the upsampled mel "lc" [B][n_rows][Lo] (dense, n_rows =
   // the loaded mel's frames x hop <= lc_rows), the upsample stages' scratch, and the cond ring
   // "lccond" [NC][L][B][64]; the loaded n_rows also lives in the device word at oSTEP + 12
@@ -1728,6 +1856,32 @@ extern "C" int lbwn_gen_set_mel(lbwn_gen_plan* p, const lbwn_params* P, void* ws
 
 extern "C" int lbwn_gen_is_persistent(const lbwn_gen_plan* p) { return p && p->persist ? 1 : 0; }
 
+extern "C" int lbwn_gen_set_sampling(lbwn_gen_plan* p, float temperature, int top_k, float top_p) {
+  LBWN_REQUIRE(p, "gen_set_sampling: plan is null");
+  LBWN_REQUIRE(std::isfinite(temperature) && temperature > 0.f,
+               "gen_set_sampling: temperature must be finite and > 0 (got %g)", (double)temperature);
+  LBWN_REQUIRE(top_k >= 0, "gen_set_sampling: top_k must be >= 0 (got %d)", top_k);
+  LBWN_REQUIRE(top_p > 0.f && top_p <= 1.f, "gen_set_sampling: top_p must be in (0, 1] (got %g)", (double)top_p);
+  p->temperature = temperature;
+  p->top_k = top_k >= p->Q ? 0 : top_k;   // every code kept: off
+  p->top_p = top_p;
+  return 0;
+}
+
+extern "C" int lbwn_gen_get_sampling(const lbwn_gen_plan* p, float* temperature, int* top_k, float* top_p) {
+  LBWN_REQUIRE(p, "gen_get_sampling: plan is null");
+  if (temperature) *temperature = p->temperature;
+  if (top_k) *top_k = p->top_k;
+  if (top_p) *top_p = p->top_p;
+  return 0;
+}
+
+static bool gen_filtered(const lbwn_gen_plan* p) { return p->temperature != 1.f || p->top_k != 0 || p->top_p != 1.f; }
+static void launch_sample(const lbwn_gen_plan* p, const DrawK& d, const long long* step, hipStream_t st) {
+  if (gen_filtered(p)) gen_sample_filt_kernel<<<p->B, 64, 0, st>>>(d, step);
+  else gen_sample_kernel<<<p->B, 64, 0, st>>>(d, step);
+}
+
 static void launch_wave(const lbwn_gen_plan* p, const WaveK& c, hipStream_t st) {
   if (p->Lo > 0) gen_wave_kernel<true><<<p->B, 512, 0, st>>>(c);
   else gen_wave_kernel<false><<<p->B, 512, 0, st>>>(c);
@@ -1774,7 +1928,7 @@ static int gen_run_gemm(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_
     if (int e = lbwn_gemm_launch(sk, 1, 0, p->gsplit[0], SPL, st)) return e;
     if (int e = lbwn_gemm_launch(p1, 1, 0, p->gsplit[1], SPL, st)) return e;
     if (int e = lbwn_gemm_launch(p2, 1, 0, p->gsplit[2], SPL, st)) return e;
-    gen_sample_kernel<<<p->B, 64, 0, st>>>(d, c.step);
+    launch_sample(p, d, c.step, st);
     LBWN_CHECK_LAUNCH();
   }
   return 0;
@@ -1788,6 +1942,7 @@ static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_s
   d.logits = gat<float>(ws, p->oLOG); d.samples = gat<int>(ws, p->oSAMP); d.wav = gat<float>(ws, p->oWAV);
   d.max_steps = p->max_steps; d.teacher = gat<int>(ws, p->oTEACH); d.n_teacher = p->n_teacher; d.seed = p->seed;
   d.code = gat<int>(ws, p->oCODE);
+  d.temperature = p->temperature; d.top_k = p->top_k; d.top_p = p->top_p;
   if (p->persist) {
     if (n_steps == 0) return 0;
     PersistK k;
@@ -1806,11 +1961,15 @@ static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_s
     k.trace = p->trace ? gat<long long>(ws, p->oTRACE) : nullptr;
     k.Bg = p->pbg;
     k.gstep = reinterpret_cast<long long*>(g + p->n_gran_core);
+    const int nblk = p->pgroups * (p->pbg + P_NH);
+    const bool filt = gen_filtered(p);
     if (p->Lo > 0) {
       k.lccond = gat<float>(ws, p->oLCC); k.NC = p->NC;
-      gen_persist_kernel<true><<<p->pgroups * (p->pbg + P_NH), 512, 0, st>>>(k);
+      if (filt) gen_persist_kernel<true, true><<<nblk, 512, 0, st>>>(k);
+      else gen_persist_kernel<true, false><<<nblk, 512, 0, st>>>(k);
     } else {
-      gen_persist_kernel<false><<<p->pgroups * (p->pbg + P_NH), 512, 0, st>>>(k);
+      if (filt) gen_persist_kernel<false, true><<<nblk, 512, 0, st>>>(k);
+      else gen_persist_kernel<false, false><<<nblk, 512, 0, st>>>(k);
     }
     LBWN_CHECK_LAUNCH();
     return 0;
@@ -1849,7 +2008,7 @@ static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_s
     gen_gemv_kernel<<<gsk, 256, 0, st>>>(sk);
     gen_gemv_kernel<<<gp1, 256, 0, st>>>(p1);
     gen_gemv_kernel<<<gp2, 256, 0, st>>>(p2);
-    gen_sample_kernel<<<p->B, 64, 0, st>>>(d, c.step);
+    launch_sample(p, d, c.step, st);
     LBWN_CHECK_LAUNCH();
   }
   return 0;

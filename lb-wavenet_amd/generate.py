@@ -11,6 +11,9 @@ conditioning (the reference's generator has none) take their mel from --mel-npy.
 the written wav then starts with the µ-law-quantised teacher instead of the draws the model made, and
 ignored, during those steps.  With --mel-npy the prefilled steps are conditioned on the mel like the
 sequential ones (upsampled row i-1 for step i).
+--temperature / --top-k / --top-p (build extensions, defaults 1 / 0 / 1 = the plain softmax draw) filter
+every step's draw: keep the top-k logits (ties kept), e = exp((l - max) / T), then the shortest
+descending prefix with mass >= top-p; --top-k 1 is greedy decoding.
 """
 import argparse
 import json
@@ -45,6 +48,14 @@ def get_args(argv=None):
                         '(shared by the batch) or [batch, frames, n_lc_in].  Upsampled mel row i-1 conditions '
                         'step i, counted from the start of the teacher (step 0 uses row 0), so it must hold '
                         'at least (steps - 1) / hop frames for the gen_seconds + teacher seconds requested')
+    p.add_argument('--temperature', type=float, default=1.0,
+                   help='(build extension) softmax temperature of the draw, finite and > 0 (1 = off)')
+    p.add_argument('--top-k', type=int, default=0,
+                   help='(build extension) draw among the k most likely codes, ties with the k-th kept '
+                        '(0 = off, 1 = greedy)')
+    p.add_argument('--top-p', type=float, default=1.0,
+                   help='(build extension) nucleus sampling: draw among the most likely codes whose mass '
+                        'reaches p, in (0, 1] (1 = off); applied after --top-k')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('ckpt', metavar='CHECKPOINT_PREFIX', type=str)
     p.add_argument('wav_dir', metavar='OUTPUT_WAV_DIR', type=str)
@@ -85,6 +96,11 @@ def main(argv=None):
     from lbwn.ckpt import ckpt_file
     from lbwn.imodel import WaveNetGen
 
+    try:
+        WaveNetGen._check_sampling(args.temperature, args.top_k, args.top_p)
+    except ValueError as e:
+        print('Bad sampling option: {}'.format(e), file=stderr)
+        sys.exit(1)
     with open(args.arch_file) as fp:
         arch = normalize_arch(json.load(fp))
     if not os.access(ckpt_file(args.ckpt), os.R_OK):                   # generate.py:43-47
@@ -116,7 +132,8 @@ def main(argv=None):
     net = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                      arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
                      args.batch_size, args.chunk_size, teacher_vec, seed=args.seed, n_lc_in=arch['n_lc_in'],
-                     n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'])
+                     n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'], temperature=args.temperature,
+                     top_k=args.top_k, top_p=args.top_p)
     print('Building graph.')
     print('Restoring from {}'.format(args.ckpt))
     net.restore(args.ckpt)

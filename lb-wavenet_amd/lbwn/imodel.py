@@ -19,8 +19,16 @@ Prompt prefill: ``prefill(codes)`` advances every stream by n known inputs in on
 that way.  On an LC arch the prefilled steps are conditioned on the loaded mel like any other step
 (``init_buffers(mel=...)`` first, or ``run(gen_sz, mel=..., prefill=True)``).  The default teacher
 path is unchanged.
+
+Sampling (keyword-only ``temperature=1.0, top_k=0, top_p=1.0``, or ``set_sampling`` later): the draw of
+every step is filtered as lbwn_gen_set_sampling defines -- top_k keeps the codes whose logit is >= the
+k-th largest (ties kept, 0 = off, >= n_quant = off), the kept codes get e = exp((l - max l) / T), top_p
+then keeps the shortest descending-e prefix with mass >= p·Σe (ties with its last member kept), and the
+inverse-CDF draw runs over the surviving e in code order.  ``top_k=1`` is greedy decoding; the neutral
+(1, 0, 1) is the unfiltered draw, bit for bit.  "logits" stays raw.
 """
 import ctypes
+import math
 import sys
 
 import numpy as np
@@ -33,7 +41,9 @@ from .arch import ParamLayout, mel_hop_sz, normalize_arch
 class WaveNetGen:
     def __init__(self, n_blocks, n_block_layers, n_quant, n_res, n_dil, n_skip, n_post1, n_gc_embed,
                  n_gc_category, use_bias, batch_sz, chunk_sz, teacher_vec=None, *, pre_bias=True, seed=0,
-                 device='cuda', graph=True, n_lc_in=0, n_lc_out=0, lc_upsample=()):
+                 device='cuda', graph=True, n_lc_in=0, n_lc_out=0, lc_upsample=(), temperature=1.0, top_k=0,
+                 top_p=1.0):
+        self.sampling = self._check_sampling(temperature, top_k, top_p)
         self.arch = normalize_arch(dict(n_blocks=n_blocks, n_block_layers=n_block_layers, n_quant=n_quant,
                                         n_res=n_res, n_dil=n_dil, n_skip=n_skip, n_post=n_post1,
                                         n_gc_embed=n_gc_embed, n_gc_category=n_gc_category, use_bias=use_bias,
@@ -110,6 +120,39 @@ class WaveNetGen:
             else:
                 setattr(P, field, base + 4 * off)
         self._params_c = P
+        self._graph = None
+        self._apply_sampling()
+        return self
+
+    # ---- sampling ---------------------------------------------------------------------------
+    @staticmethod
+    def _check_sampling(temperature, top_k, top_p):
+        """(float T, int k, float p) or ValueError naming the argument.  No library call."""
+        try:
+            T, p = float(temperature), float(top_p)
+        except (TypeError, ValueError):
+            raise ValueError('temperature and top_p must be numbers, got %r and %r' % (temperature, top_p))
+        if not (math.isfinite(T) and T > 0):
+            raise ValueError('temperature must be finite and > 0, got %r' % (temperature,))
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
+            raise ValueError('top_k must be an integer >= 0, got %r' % (top_k,))
+        if not (0 < p <= 1):
+            raise ValueError('top_p must be in (0, 1], got %r' % (top_p,))
+        return T, int(top_k), p
+
+    def _apply_sampling(self):
+        T, k, p = self.sampling
+        _lib.check(self.lib.lbwn_gen_set_sampling(self._plan, T, k, p))
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None):
+        """Change the draw's filters (None keeps the current value) for the steps run from now on.
+        The plan reads them at launch, so a captured graph holds the old ones: it is dropped and the
+        next ``step`` captures again."""
+        T, k, p = self.sampling
+        self.sampling = self._check_sampling(T if temperature is None else temperature,
+                                             k if top_k is None else top_k, p if top_p is None else top_p)
+        if self._plan is not None:
+            self._apply_sampling()
         self._graph = None
         return self
 

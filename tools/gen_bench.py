@@ -1,7 +1,8 @@
 """Cached generation timing: arch3 (or --arch), B streams, N steps after a warm chunk,
 graph replay; prints us/step.  Run under rocprofv3 --kernel-trace --stats for the split.
 Archs with local conditioning get a random mel long enough for the run; --no-lc drops the
-arch's LC (the same stack without the mel term, for A/B runs)."""
+arch's LC (the same stack without the mel term, for A/B runs).  --temperature / --top-k / --top-p
+select the filtered draw (WaveNetGen.set_sampling; defaults 1 / 0 / 1 = the plain draw)."""
 import argparse
 import os
 import sys
@@ -21,6 +22,9 @@ ap.add_argument('--steps', type=int, default=4000)
 ap.add_argument('--chunk', type=int, default=1000)
 ap.add_argument('--no-graph', action='store_true')
 ap.add_argument('--no-lc', action='store_true')
+ap.add_argument('--temperature', type=float, default=1.0)
+ap.add_argument('--top-k', type=int, default=0)
+ap.add_argument('--top-p', type=float, default=1.0)
 a = ap.parse_args()
 arch = load_arch(a.arch)
 if a.no_lc:
@@ -29,7 +33,8 @@ net = WaveNetTrain(**arch, batch_sz=1, l2_factor=0.0, print_interval=0, seed=0)
 g = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
                a.batch, a.chunk, None, seed=1, graph=not a.no_graph, n_lc_in=arch['n_lc_in'],
-               n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'])
+               n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'], temperature=a.temperature,
+               top_k=a.top_k, top_p=a.top_p)
 g.load_params(net)
 g.build_graph(a.steps + a.chunk)
 gc = list(range(1, a.batch + 1)) if arch['n_gc_embed'] else None
@@ -44,4 +49,5 @@ t0 = time.perf_counter()
 g.step(a.steps)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
-print('B=%d steps=%d  %.2f us/step  %.0f samples/s' % (a.batch, a.steps, dt / a.steps * 1e6, a.batch * a.steps / dt))
+print('B=%d steps=%d  %.2f us/step  %.0f samples/s  sampling=(%g, %d, %g)'
+      % (a.batch, a.steps, dt / a.steps * 1e6, a.batch * a.steps / dt, a.temperature, a.top_k, a.top_p))

@@ -1,7 +1,8 @@
 """Wall-clock trace of one cached-generation step (LBWN_GEN_TRACE=1, set here), arch3, B
 streams.  Persistent form (default for B <= 80, groups of <= 16): the run's last step as seen by chain block 0
 and the last head block; per-step form (LBWN_GEN_PERSIST=0): per-layer cycles of stream 0's
-gen_wave and the GEMV stamps.  Usage: python tools/gen_trace.py [B]"""
+gen_wave and the GEMV stamps.  Usage: python tools/gen_trace.py [B [temperature top_k top_p]]
+(the sampling triple selects the filtered draw: "barrier D passed" to "draw done" is the draw)."""
 import os
 import sys
 
@@ -16,10 +17,11 @@ from lbwn.tmodel import WaveNetTrain  # noqa: E402
 
 arch = load_arch(os.path.join(ROOT, 'par', 'arch3.json'))
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+T, top_k, top_p = (float(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4])) if len(sys.argv) > 4 else (1.0, 0, 1.0)
 net = WaveNetTrain(**arch, batch_sz=1, l2_factor=0.0, print_interval=0, seed=0)
 g = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
-               B, 200, None, seed=1, graph=False)
+               B, 200, None, seed=1, graph=False, temperature=T, top_k=top_k, top_p=top_p)
 g.load_params(net)
 g.build_graph(4000)
 g.init_buffers(list(range(1, B + 1)) if arch['n_gc_embed'] else None)
@@ -34,7 +36,8 @@ for _ in range(5):
 tr = np.median(np.array(runs), axis=0)
 if g.persistent:
     us = lambda x: (x - tr[0]) / 100.0   # noqa: E731  (wall_clock64: 100 MHz)
-    print('persistent, B=%d; us from chain block 0 starting step n-1 (after its draw):' % B)
+    print('persistent, B=%d, sampling (%g, %d, %g); us from chain block 0 starting step n-1 (after its draw):'
+          % (B, T, top_k, top_p))
     lay = np.diff(np.concatenate([[tr[0]], tr[8:8 + L]])) / 100.0
     print('  chain 0: layers end %.2f  (per layer median %.3f us, first %.3f)' % (us(tr[1]), np.median(lay), lay[0]))
     nr = 1 + (L - 1 + 7) // 8
