@@ -145,7 +145,7 @@ size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* plan);
 /* "samples" int32 [B][max_steps] (drawn µ-law codes), "wav" fp32 [B][max_steps]
  * (mu_decode of the draws, imodel.py:181-182), "logits" [B][Q] (last step), "step" int64,
  * "rings" (lookback state, SAVE layout), "teacher" int32, "status" int32 (0; 5 when a persistent
- * hand-off timed out); LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
+ * hand-off timed out; 6 when lbwn_gen_state_load refused its snapshot or map); LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
  * ([B][rows][n_lc_out] bytes), of which lbwn_gen_set_mel fills the first B·n_frames·hop rows
  * densely as [B][n_frames·hop][n_lc_out], and "lccond" fp32 [NC][L][B][64] (slot = step mod NC;
  * columns: signal 0..31 | gate 32..63, zero past n_dil) and "pfcond" fp32 [B·T_s][G·2·n_dil], the
@@ -238,6 +238,42 @@ int lbwn_gen_set_sampling(lbwn_gen_plan* plan, float temperature, int top_k, flo
 /* The plan's normalised values (a top_k >= n_quant reads back as 0); NULL outputs are skipped.
  * EINVAL when plan is NULL. */
 int lbwn_gen_get_sampling(const lbwn_gen_plan* plan, float* temperature, int* top_k, float* top_p);
+/* Save, restore and fan out the state of a run (added after ABI 5 was declared, same ABI: three symbols
+ * added, none altered).  Between two launches a run is the lookback rings, every stream's
+ * pending input code, the step counter and the persistent stream groups' copies of it; the rest of the
+ * workspace is recomputed by every launch or set by lbwn_gen_start / _set_mel / _set_sampling.
+ * The snapshot is caller-owned device memory, 16-byte aligned, not overlapping the workspace, and
+ * stream-major, so it does not depend on the batch size of the plan that wrote it:
+ *   header, 256 bytes: int32 magic 0x5453424c ("LBST"), layout version 1, n_streams, n_blocks,
+ *     n_block_layers, n_res, n_quant, record_bytes; int64 step at byte 32; the rest zero;
+ *   n_streams records of record_bytes = round_up_16(16 + 4·D·n_res), D = n_blocks·(2^n_block_layers - 1):
+ *     the pending code (int32; -1: the zero vector after lbwn_gen_start), 12 zero bytes, then the stream's
+ *     rings in layer order, layer (block, bl) with d = 2^bl as fp32 [d][n_res], slot = step mod d; zero
+ *     bytes up to record_bytes.
+ * lbwn_gen_state_bytes: 256 + n_streams·record_bytes; 0 for a NULL plan or n_streams < 1.
+ * lbwn_gen_state_save writes all batch_sz streams (one launch; the step is read on the device) and
+ * changes nothing in the workspace.
+ * lbwn_gen_state_load must follow lbwn_gen_start on this workspace (which supplies the packed images, GC
+ * projections, seed, pre_bias and teacher; LC plans also load the mel with lbwn_gen_set_mel before the
+ * next run).  Stream b takes record src_stream[b] (device int32 [batch_sz], entries in
+ * [0, state_streams); several streams may take one record; NULL = identity, state_streams == batch_sz).
+ * Afterwards the rings and pending codes are the records', the step counter and every persistent group's
+ * are the header's step, and every hand-off granule is zero (a granule left by the run that was here could
+ * carry the tag the loaded step polls for).  "samples", "wav", "logits", "teacher", "lc", "status" and all
+ * host state are untouched.  The uniform of a draw stays splitmix64(seed, destination stream, step): an
+ * identity load continues exactly as the saved run did, two streams loaded from one record continue
+ * differently.  A captured lbwn_gen_run stays valid across a load (it reads the step on the device).
+ * Both are stream-ordered, without host synchronisation or allocation, and graph-capturable.
+ * EINVAL before any launch, naming the argument: plan, workspace or state NULL, state not 16-byte
+ * aligned, state_streams < 1, src_stream NULL with state_streams != batch_sz.  The header is device
+ * memory, so the load's launch checks it before it writes: magic, version, n_blocks, n_block_layers,
+ * n_res, n_quant and record_bytes against the plan, n_streams against state_streams, 0 <= step <=
+ * max_steps, every map entry in range.  On a mismatch "status" becomes 6 and nothing else in the
+ * workspace changes; the step launches stop on a nonzero status and lbwn_gen_start clears it. */
+size_t lbwn_gen_state_bytes(const lbwn_gen_plan* plan, int n_streams);
+int lbwn_gen_state_save(const lbwn_gen_plan* plan, const void* workspace, void* state, void* stream);
+int lbwn_gen_state_load(lbwn_gen_plan* plan, void* workspace, const void* state, int state_streams,
+                        const int* src_stream, void* stream);
 
 /* ---- fine-grained kernels (parity tests, custom drivers) ------------------------------ */
 /* ops.mu_encode_np (ops.py:23-28, tf32=0, float64 math) / ops.mu_encode (ops.py:4-9, tf32=1) */

@@ -21,6 +21,8 @@
 // decode, next input = teacher[t] or the draw (imodel.py:167-187, :260-269).  A sampling triple other
 // than (1, 0, 1) (lbwn_gen_set_sampling: temperature, top_k, top_p) selects the FILT instantiations,
 // whose draw filters the codes first (draw_core_filt); the neutral triple runs the plain ones.
+// State snapshots (lbwn_gen_state_save / _load): one transposing copy kernel between the layer-major
+// rings and stream-major records, after the prefill's kernels; the step kernels know nothing of it.
 // Prompt prefill (lbwn_gen_prefill): n steps with known inputs as a sliced per-layer forward
 // (layer.hip's layer_fwd_kernel) whose D-separation state is the rings; its kernels are at the end
 // of the namespace below, the step kernels know nothing of it.  LC plans project the slice's lc
@@ -31,6 +33,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -1552,6 +1555,112 @@ __global__ void gen_prefill_finish_kernel(const int* codes, long ld_codes, long 
   if (threadIdx.x == 0) *step = t1;
 }
 
+// ---- state snapshot (lbwn_gen_state_save / lbwn_gen_state_load) ----------------
+// What a run is between two launches: the rings, the pending codes, the step counter (and the
+// persistent groups' copies of it).  The snapshot is stream-major -- a 256-byte header, then per
+// stream a record {code, 12 zero bytes, the stream's rings in layer order, each [d][Cr]} -- so it
+// does not depend on the batch size of the plan that wrote it.  Position p (in rows of Cr floats) of
+// a record, with m = 2^nbl - 1: block = p / m, r = p % m, bl = floor(log2(r + 1)), slot = r + 1 - 2^bl;
+// the workspace row is (block·m + 2^bl - 1)·B + b·2^bl + slot (the layers before it, then [B][d]).
+constexpr int GS_MAGIC = 0x5453424c;   // "LBST"
+constexpr int GS_VERSION = 1;
+constexpr int GS_HEADER = 256;         // bytes; int32 words 0..7 below, the step as int64 at byte 32
+constexpr int GS_CODE = 16;            // bytes of a record before its rings
+constexpr int GS_UNROLL = 4;           // independent loads per thread before the first store
+constexpr int GS_STATUS = 6;           // "status" after a refused load
+
+struct StateK {
+  float* rings; int* code; long long* step; long long* gstep; int* status;
+  unsigned long long* gran; long n_gran;   // the hand-off granules a load zeroes (without the groups' counters)
+  char* state; const int* map;             // the snapshot; load: stream b takes record map[b] (null: b)
+  long long max_steps;
+  int B, nb, nbl, Cr, Q, rec_bytes, state_streams, ngroups;
+};
+
+// a load's refusals, by every block for itself before it writes anything: the header against the plan
+// and the call, every map entry in range
+LBWN_DEV bool state_refused(const StateK& a) {
+  const int* h = reinterpret_cast<const int*>(a.state);
+  const long long t = *reinterpret_cast<const long long*>(a.state + 32);
+  int bad = !(h[0] == GS_MAGIC && h[1] == GS_VERSION && h[2] == a.state_streams && h[3] == a.nb && h[4] == a.nbl &&
+              h[5] == a.Cr && h[6] == a.Q && h[7] == a.rec_bytes && t >= 0 && t <= a.max_steps);
+  if (a.map)
+    for (int b = threadIdx.x; b < a.B; b += blockDim.x) bad |= a.map[b] < 0 || a.map[b] >= a.state_streams;
+  return __syncthreads_or(bad) != 0;
+}
+
+// V4: 16 bytes per lane (Cr % 4 == 0, both sides 16-byte aligned), else 4.  LOAD: snapshot -> workspace
+// (plus the granules, the codes and the counters), else workspace -> snapshot (plus the header).
+template <bool V4, bool LOAD>
+__global__ __launch_bounds__(256) void gen_state_copy_kernel(StateK a) {
+  if (LOAD && state_refused(a)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.status = GS_STATUS;
+    return;
+  }
+  typedef typename std::conditional<V4, floatx4, float>::type T;
+  const int cw = V4 ? a.Cr >> 2 : a.Cr, m = (1 << a.nbl) - 1;
+  const long per = (long)a.nb * m * cw, total = (long)a.B * per;   // items of one record, of the call
+  const long stride = (long)gridDim.x * blockDim.x;
+  auto ends = [&](long e, T*& w, T*& s) {   // the workspace and snapshot ends of item e
+    const int b = (int)(e / per);
+    const long r = e % per;
+    const int c = (int)(r % cw), p = (int)(r / cw);
+    const int rr = p % m, bl = 31 - __clz(rr + 1), slot = rr + 1 - (1 << bl);
+    const long row = ((long)(p - rr) + (1 << bl) - 1) * a.B + ((long)b << bl) + slot;
+    const long rec = LOAD && a.map ? a.map[b] : b;
+    w = reinterpret_cast<T*>(a.rings + row * a.Cr) + c;
+    s = reinterpret_cast<T*>(a.state + GS_HEADER + rec * a.rec_bytes + GS_CODE + 4L * p * a.Cr) + c;
+  };
+  for (long e0 = blockIdx.x * (long)blockDim.x + threadIdx.x; e0 < total; e0 += GS_UNROLL * stride) {
+    T v[GS_UNROLL];
+    T* dst[GS_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GS_UNROLL; ++u) {
+      const long e = e0 + u * stride;
+      dst[u] = nullptr;
+      if (e < total) {
+        T *w, *s;
+        ends(e, w, s);
+        v[u] = LOAD ? *s : *w;
+        dst[u] = LOAD ? w : s;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GS_UNROLL; ++u)
+      if (dst[u]) *dst[u] = v[u];
+  }
+  if (LOAD) {   // no granule of the run that was here may carry a tag the loaded step polls for
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < a.n_gran; e += stride) a.gran[e] = 0ull;
+  }
+  if (blockIdx.x != 0) return;
+  int* h = reinterpret_cast<int*>(a.state);
+  if (LOAD) {
+    const long long t = *reinterpret_cast<const long long*>(a.state + 32);
+    for (int b = threadIdx.x; b < a.B; b += blockDim.x) {
+      const long rec = a.map ? a.map[b] : b;
+      const int c = *reinterpret_cast<const int*>(a.state + GS_HEADER + rec * a.rec_bytes);
+      a.code[b] = min(max(c, -1), a.Q - 1);   // what the step kernels may read: -1 or inside PRE
+    }
+    for (int g = threadIdx.x; g < a.ngroups - 1; g += blockDim.x) a.gstep[g] = t;
+    if (threadIdx.x == 0) *a.step = t;
+  } else {
+    const int pad = (a.rec_bytes - GS_CODE) / 4 - a.nb * m * a.Cr;   // floats behind a record's rings (n_res % 4 != 0)
+    for (int b = threadIdx.x; b < a.B; b += blockDim.x) {
+      int* r = reinterpret_cast<int*>(a.state + GS_HEADER + (long)b * a.rec_bytes);
+      r[0] = a.code[b];
+      r[1] = r[2] = r[3] = 0;
+      for (int i = 0; i < pad; ++i) r[a.rec_bytes / 4 - 1 - i] = 0;
+    }
+    if (threadIdx.x == 0) {
+      h[0] = GS_MAGIC; h[1] = GS_VERSION; h[2] = a.B; h[3] = a.nb; h[4] = a.nbl; h[5] = a.Cr; h[6] = a.Q;
+      h[7] = a.rec_bytes;
+      *reinterpret_cast<long long*>(a.state + 32) = *a.step;
+    } else if (threadIdx.x >= 10 && threadIdx.x < GS_HEADER / 4) {
+      h[threadIdx.x] = 0;
+    }
+  }
+}
+
 }  // namespace
 
 // ---- host side: generation plan ----------------------------------------------------------
@@ -1594,6 +1703,7 @@ struct lbwn_gen_plan {
   // LC plans: the projected LC terms of one slice for pfG consecutive layers, "pfcond" [B·pfT][pfG·2·Cd]
   int pfT = 0, pfH = 0, pfG = 0;
   size_t oPFX[2] = {0, 0}, oPFZ = 0, oPFIMG = 0, oPFGC = 0, oPFIDS = 0, oPFCOND = 0;
+  int ncu = 0;   // the device's CUs at plan creation (0: none seen), the state copies' grid
 };
 
 constexpr int G_LC_CHUNK = 64;         // default NC (steps per projection launch / persistent sub-run)
@@ -1705,6 +1815,7 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   p->pbg = (B + p->pgroups - 1) / p->pgroups;
   p->persist = (!pe || strcmp(pe, "0") != 0) && p->L <= P_MAXL && p->Q <= 256 && p->Cs <= 16 * P_NH &&
                p->Cp <= 16 * P_NH && have_dev && p->pgroups * (p->pbg + P_NH) <= ncu;
+  p->ncu = have_dev ? ncu : 0;
   p->n_gran_core = (long)B * p->L * 32 + (long)B * p->Cs + (long)P_NH * B * p->Q;
   p->n_gran = p->n_gran_core + p->pgroups;   // + the groups' step counters (zeroed with the granules)
   p->oGRAN = gcarve(cur, 8 * (size_t)p->n_gran);
@@ -1765,7 +1876,8 @@ extern "C" int lbwn_gen_tensor(const lbwn_gen_plan* p, const char* name, size_t*
   else if (!strcmp(name, "wav")) { *off = p->oWAV; *bytes = 4 * B * p->max_steps; }
   else if (!strcmp(name, "logits")) { *off = p->oLOG; *bytes = 4 * B * p->Q; }
   else if (!strcmp(name, "step")) { *off = p->oSTEP; *bytes = 8; }
-  else if (!strcmp(name, "status")) { *off = p->oSTEP + 8; *bytes = 4; }   // 0, or 5: a persistent hand-off timed out
+  // 0, or 5: a persistent hand-off timed out, or 6: lbwn_gen_state_load refused its snapshot or map
+  else if (!strcmp(name, "status")) { *off = p->oSTEP + 8; *bytes = 4; }
   else if (!strcmp(name, "trace")) { *off = p->oTRACE; *bytes = 8 * (size_t)(2 * p->L + 8 + 128 + 2 * P_NH); }
   else if (!strcmp(name, "rings")) { *off = p->oRING; *bytes = 4 * (size_t)p->n_ring; }
   else if (!strcmp(name, "teacher")) { *off = p->oTEACH; *bytes = 4 * (size_t)std::max<long long>(1, p->n_teacher); }
@@ -2137,6 +2249,71 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
   unsigned long long* g = gat<unsigned long long>(ws, p->oGRAN);
   gen_prefill_finish_kernel<<<1, 256, 0, st>>>(codes, (long)ld_codes, (long)n, code, step,
                                                reinterpret_cast<long long*>(g + p->n_gran_core), p->pgroups, B, p->Q);
+  LBWN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- state snapshot ---------------------------------------------------------------------------
+static size_t state_record_bytes(const lbwn_gen_plan* p) {
+  const size_t rows = (size_t)p->a.n_blocks * (((size_t)1 << p->nbl) - 1);
+  return (GS_CODE + 4 * rows * p->Cr + 15) / 16 * 16;
+}
+
+extern "C" size_t lbwn_gen_state_bytes(const lbwn_gen_plan* p, int n_streams) {
+  return p && n_streams >= 1 ? GS_HEADER + (size_t)n_streams * state_record_bytes(p) : 0;
+}
+
+static StateK state_args(const lbwn_gen_plan* p, void* ws, void* state) {
+  StateK k;
+  memset(&k, 0, sizeof(k));
+  unsigned long long* g = gat<unsigned long long>(ws, p->oGRAN);
+  k.rings = gat<float>(ws, p->oRING); k.code = gat<int>(ws, p->oCODE); k.step = gat<long long>(ws, p->oSTEP);
+  k.gstep = reinterpret_cast<long long*>(g + p->n_gran_core); k.status = gat<int>(ws, p->oSTEP + 8);
+  k.gran = g; k.n_gran = p->n_gran_core;
+  k.state = static_cast<char*>(state);
+  k.max_steps = p->max_steps;
+  k.B = p->B; k.nb = p->a.n_blocks; k.nbl = p->nbl; k.Cr = p->Cr; k.Q = p->Q;
+  k.rec_bytes = (int)state_record_bytes(p); k.state_streams = p->B; k.ngroups = p->pgroups;
+  return k;
+}
+
+// a grid sized to the CUs (8 blocks of 4 waves each), or to the items when those are fewer
+static int state_grid(const lbwn_gen_plan* p, bool v4) {
+  const long items = p->n_ring / (v4 ? 4 : 1);
+  const long want = (items + 256L * GS_UNROLL - 1) / (256L * GS_UNROLL);
+  return (int)std::max(1L, std::min(want, 8L * (p->ncu > 0 ? p->ncu : 256)));
+}
+
+extern "C" int lbwn_gen_state_save(const lbwn_gen_plan* p, const void* ws, void* state, void* stream) {
+  LBWN_REQUIRE(p, "gen_state_save: plan is null");
+  LBWN_REQUIRE(ws, "gen_state_save: workspace is null");
+  LBWN_REQUIRE(state, "gen_state_save: state is null");
+  LBWN_REQUIRE((((uintptr_t)state) & 15) == 0, "gen_state_save: state %p is not 16-byte aligned", state);
+  hipStream_t st = (hipStream_t)stream;
+  const StateK k = state_args(p, const_cast<void*>(ws), state);
+  const bool v4 = p->Cr % 4 == 0 && (((uintptr_t)ws) & 15) == 0;
+  if (v4) gen_state_copy_kernel<true, false><<<state_grid(p, true), 256, 0, st>>>(k);
+  else gen_state_copy_kernel<false, false><<<state_grid(p, false), 256, 0, st>>>(k);
+  LBWN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int lbwn_gen_state_load(lbwn_gen_plan* p, void* ws, const void* state, int state_streams,
+                                   const int* src_stream, void* stream) {
+  LBWN_REQUIRE(p, "gen_state_load: plan is null");
+  LBWN_REQUIRE(ws, "gen_state_load: workspace is null");
+  LBWN_REQUIRE(state, "gen_state_load: state is null");
+  LBWN_REQUIRE(state_streams >= 1, "gen_state_load: state_streams must be >= 1 (got %d)", state_streams);
+  LBWN_REQUIRE(src_stream || state_streams == p->B,
+               "gen_state_load: src_stream is null (identity) but state_streams %d != batch_sz %d", state_streams, p->B);
+  LBWN_REQUIRE((((uintptr_t)state) & 15) == 0, "gen_state_load: state %p is not 16-byte aligned", state);
+  hipStream_t st = (hipStream_t)stream;
+  StateK k = state_args(p, ws, const_cast<void*>(state));   // LOAD only reads it
+  k.state_streams = state_streams;
+  k.map = src_stream;
+  const bool v4 = p->Cr % 4 == 0 && (((uintptr_t)ws) & 15) == 0;
+  if (v4) gen_state_copy_kernel<true, true><<<state_grid(p, true), 256, 0, st>>>(k);
+  else gen_state_copy_kernel<false, true><<<state_grid(p, false), 256, 0, st>>>(k);
   LBWN_CHECK_LAUNCH();
   return 0;
 }

@@ -14,6 +14,9 @@ sequential ones (upsampled row i-1 for step i).
 --temperature / --top-k / --top-p (build extensions, defaults 1 / 0 / 1 = the plain softmax draw) filter
 every step's draw: keep the top-k logits (ties kept), e = exp((l - max) / T), then the shortest
 descending prefix with mass >= top-p; --top-k 1 is greedy decoding.
+--prefill-fanout (build extension; implies the prefill path, needs --teacher-wav) prefills the teacher
+once per distinct voice id and copies that state to every stream of the voice (WaveNetGen.run(...,
+prefill='fanout')); with --mel-npy only the shared [frames, n_lc_in] shape.
 """
 import argparse
 import json
@@ -33,6 +36,10 @@ def get_args(argv=None):
                    help='(build extension) run the teacher\'s steps as one parallel prefill instead of '
                         'one step at a time; the written wav then starts with the mu-law-quantised teacher '
                         '(without it: with the draws the model made, and ignored, during those steps)')
+    p.add_argument('--prefill-fanout', action='store_true',
+                   help='(build extension) prefill the teacher once per distinct voice id and fan the state '
+                        'out to the batch (implies the prefill path; needs --teacher-wav; --mel-npy must be '
+                        'the shared [frames, n_lc_in] shape)')
     p.add_argument('--teacher-start', '-ts', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--teacher-duration', '-td', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--gen-seconds', '-g', type=float, default=5, help='Number of additional seconds to generate')
@@ -101,6 +108,9 @@ def main(argv=None):
     except ValueError as e:
         print('Bad sampling option: {}'.format(e), file=stderr)
         sys.exit(1)
+    if args.prefill_fanout and args.teacher_wav is None:
+        print('--prefill-fanout needs --teacher-wav: there is no prompt to prefill', file=stderr)
+        sys.exit(1)
     with open(args.arch_file) as fp:
         arch = normalize_arch(json.load(fp))
     if not os.access(ckpt_file(args.ckpt), os.R_OK):                   # generate.py:43-47
@@ -128,6 +138,10 @@ def main(argv=None):
                 tuple(mel.shape), gen_sz, args.gen_seconds, teacher_seconds, -(-(gen_sz - 1) // hop), hop),
                 file=stderr)
             sys.exit(1)
+        if args.prefill_fanout and mel.ndim != 2:
+            print('--prefill-fanout takes the shared mel shape [frames, n_lc_in] only, got {}'.format(
+                tuple(mel.shape)), file=stderr)
+            sys.exit(1)
 
     net = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                      arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
@@ -141,7 +155,7 @@ def main(argv=None):
     ids = [int(v) for v in args.gc_ids.split(',') if v.strip()]
     gc_ids = [ids[i % len(ids)] for i in range(args.batch_size)] if arch['n_gc_embed'] else None
     print('Starting inference...')
-    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel, prefill=args.teacher_prefill)
+    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel, prefill='fanout' if args.prefill_fanout else args.teacher_prefill)
     wav_streams = wav_streams.cpu().numpy()
 
     from scipy.io import wavfile

@@ -84,6 +84,9 @@ _SIGS = {
     'lbwn_gen_set_sampling': (c_int, [c_void_p, c_float, c_int, c_float]),
     'lbwn_gen_get_sampling': (c_int, [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_float)]),
+    'lbwn_gen_state_bytes': (c_size_t, [c_void_p, c_int]),
+    'lbwn_gen_state_save': (c_int, [c_void_p, c_fp, c_fp, c_void_p]),
+    'lbwn_gen_state_load': (c_int, [c_void_p, c_fp, c_fp, c_int, c_fp, c_void_p]),
     'lbwn_mulaw_encode':(c_int, [c_fp, c_fp, c_int64, c_int, c_int, c_void_p]),
     'lbwn_mulaw_decode': (c_int, [c_fp, c_fp, c_int64, c_int, c_void_p]),
     'lbwn_gemm_f32': (c_int, [c_fp, c_int64, c_int, c_fp, c_int64, c_int, c_fp, c_int64, c_int, c_int, c_int,

@@ -26,6 +26,12 @@ k-th largest (ties kept, 0 = off, >= n_quant = off), the kept codes get e = exp(
 then keeps the shortest descending-e prefix with mass >= p·Σe (ties with its last member kept), and the
 inverse-CDF draw runs over the surviving e in code order.  ``top_k=1`` is greedy decoding; the neutral
 (1, 0, 1) is the unfiltered draw, bit for bit.  "logits" stays raw.
+
+State (lbwn_gen_state_save / _load): ``save_state()`` returns a ``GenState`` -- the rings, the
+pending codes and the step of every stream, stream-major, so it loads into a plan of another batch size;
+``load_state(state, streams)`` gives stream b the record ``streams[b]``; ``fork(src)`` is both at once.
+``run(gen_sz, prefill='fanout')`` prefills the teacher once per distinct voice id in a private generator
+and loads that state into every stream of the voice.
 """
 import ctypes
 import math
@@ -36,6 +42,74 @@ import torch
 
 from . import _lib
 from .arch import ParamLayout, mel_hop_sz, normalize_arch
+
+
+STATE_MAGIC = 0x5453424c      # "LBST" (include/lbwn.h, lbwn_gen_state_save)
+STATE_VERSION = 1
+STATE_HEADER = 256
+STATE_DIMS = ('n_blocks', 'n_block_layers', 'n_res', 'n_quant')
+
+
+def state_record_bytes(n_blocks, n_block_layers, n_res):
+    """Bytes of one stream's record: the pending code (16 bytes) and its rings, rounded up to 16."""
+    return (16 + 4 * n_blocks * (2 ** n_block_layers - 1) * n_res + 15) // 16 * 16
+
+
+def parse_state_header(raw):
+    """The 256 header bytes (uint8 array) of a snapshot -> dict(n_streams, n_blocks, n_block_layers, n_res,
+    n_quant, record_bytes, step); ValueError when they are not a version-1 header."""
+    raw = np.ascontiguousarray(np.asarray(raw, np.uint8).reshape(-1)[:STATE_HEADER])
+    if raw.size < STATE_HEADER:
+        raise ValueError('state: %d bytes are shorter than the %d-byte header' % (raw.size, STATE_HEADER))
+    w = raw[:32].view('<i4')
+    if int(w[0]) != STATE_MAGIC:
+        raise ValueError('state: bad magic 0x%08x (want 0x%08x)' % (int(w[0]) & 0xffffffff, STATE_MAGIC))
+    if int(w[1]) != STATE_VERSION:
+        raise ValueError('state: layout version %d, this build reads %d' % (int(w[1]), STATE_VERSION))
+    h = dict(zip(('n_streams',) + STATE_DIMS + ('record_bytes',), (int(v) for v in w[2:8])))
+    h['step'] = int(raw[32:40].view('<i8')[0])
+    if h['n_streams'] < 1 or h['record_bytes'] != state_record_bytes(h['n_blocks'], h['n_block_layers'], h['n_res']):
+        raise ValueError('state: inconsistent header %r' % (h,))
+    return h
+
+
+class GenState:
+    """A snapshot written by lbwn_gen_state_save: ``blob`` is the uint8 tensor in the documented layout
+    (256-byte header, then n_streams stream-major records), ``dims`` the arch dimensions it belongs to."""
+
+    def __init__(self, blob, n_streams, n_blocks, n_block_layers, n_res, n_quant):
+        self.blob = blob
+        self.n_streams = int(n_streams)
+        self.dims = dict(n_blocks=int(n_blocks), n_block_layers=int(n_block_layers), n_res=int(n_res),
+                         n_quant=int(n_quant))
+        self.record_bytes = state_record_bytes(self.dims['n_blocks'], self.dims['n_block_layers'], self.dims['n_res'])
+        want = STATE_HEADER + self.n_streams * self.record_bytes
+        if blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != want:
+            raise ValueError('state: blob must be uint8 [%d], got %s %s' % (want, blob.dtype, tuple(blob.shape)))
+
+    def header(self):
+        """The parsed header (one device synchronisation)."""
+        return parse_state_header(self.blob[:STATE_HEADER].cpu().numpy())
+
+    def step(self):
+        """The step the snapshot was taken at (one device synchronisation)."""
+        return self.header()['step']
+
+    def save(self, path):
+        """Write the blob with np.save (a .npy of uint8; numpy appends '.npy' to a path without it)."""
+        np.save(path, self.blob.cpu().numpy(), allow_pickle=False)
+
+    @classmethod
+    def load(cls, path, device='cuda'):
+        """Read a snapshot written by ``save`` (no pickle); the header says whose it is."""
+        a = np.load(path, allow_pickle=False)
+        if a.dtype != np.uint8 or a.ndim != 1:
+            raise ValueError('state file %s: expected a 1-D uint8 array, got %s %s' % (path, a.dtype, a.shape))
+        h = parse_state_header(a)
+        if a.size != STATE_HEADER + h['n_streams'] * h['record_bytes']:
+            raise ValueError('state file %s: %d bytes, the header says %d' % (
+                path, a.size, STATE_HEADER + h['n_streams'] * h['record_bytes']))
+        return cls(torch.from_numpy(a).to(device), h['n_streams'], *(h[k] for k in STATE_DIMS))
 
 
 class WaveNetGen:
@@ -71,6 +145,9 @@ class WaveNetGen:
         self._ws = None
         self._graph = None
         self._mel = None      # the mel loaded by the last init_buffers (None: none since lbwn_gen_start)
+        self._started = False   # init_buffers (lbwn_gen_start) ran on the current plan
+        self._state_keep = None   # the snapshot and map of the last load_state: its launch reads them in stream order
+        self._fan = None        # (n_voices, n), the private generator of the last fan-out prefill
 
     # ---- parameters -------------------------------------------------------------------------
     def load_params(self, src):
@@ -121,6 +198,7 @@ class WaveNetGen:
                 setattr(P, field, base + 4 * off)
         self._params_c = P
         self._graph = None
+        self._started = False
         self._apply_sampling()
         return self
 
@@ -228,14 +306,120 @@ class WaveNetGen:
                                              _lib.stream_ptr()))
         return n
 
+    # ---- state ------------------------------------------------------------------------------
+    def _state_dims(self):
+        return {k: int(self.arch[k]) for k in STATE_DIMS}
+
+    def _check_map(self, streams, n_src, what):
+        """``streams`` as a list of batch_sz ints in [0, n_src) (None: identity, n_src == batch_sz);
+        ValueError otherwise.  No library call."""
+        if streams is None:
+            if n_src != self.batch_sz:
+                raise ValueError('%s: streams=None (identity) needs a state of batch_sz = %d streams, got %d'
+                                 % (what, self.batch_sz, n_src))
+            return None
+        try:
+            m = list(streams)
+        except TypeError:
+            raise ValueError('%s: streams must be a list of %d stream indices, got %r' % (what, self.batch_sz, streams))
+        if len(m) != self.batch_sz:
+            raise ValueError('%s: streams has %d entries, batch_sz is %d' % (what, len(m), self.batch_sz))
+        for b, s in enumerate(m):
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < n_src:
+                raise ValueError('%s: streams[%d] = %r is not an integer in [0, %d)' % (what, b, s, n_src))
+        return [int(s) for s in m]
+
+    def save_state(self):
+        """The state of the run as a ``GenState`` (lbwn_gen_state_save, on the current stream): every
+        stream's rings and pending code and the step.  "samples" / "wav" are not part of it."""
+        if self._plan is None:
+            raise ValueError('save_state: no plan (build_graph and init_buffers first)')
+        nb = self.lib.lbwn_gen_state_bytes(self._plan, self.batch_sz)
+        blob = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.lbwn_gen_state_save(self._plan, self._ws.data_ptr(), blob.data_ptr(), _lib.stream_ptr()))
+        return GenState(blob, self.batch_sz, **self._state_dims())
+
+    def load_state(self, state, streams=None):
+        """Stream b continues from record ``streams[b]`` of ``state`` (None: record b) at the state's step
+        (lbwn_gen_state_load, on the current stream; after init_buffers, which supplies everything that is
+        not state).  Draws stay keyed by the destination stream, so streams loaded from one record continue
+        differently.  A captured graph stays valid.  A snapshot the device refuses sets status 6
+        (``check_status``)."""
+        if self._plan is None:
+            raise ValueError('load_state: no plan (build_graph and init_buffers first)')
+        if not isinstance(state, GenState):
+            raise ValueError('load_state: state must be a GenState, got %s' % type(state).__name__)
+        if state.dims != self._state_dims():
+            raise ValueError('load_state: the state belongs to another arch (%r, this plan has %r)'
+                             % (state.dims, self._state_dims()))
+        m = self._check_map(streams, state.n_streams, 'load_state')
+        if not self._started:
+            raise RuntimeError('load_state: init_buffers first (it supplies the images, GC projections and seed)')
+        blob = state.blob.to(self.device)
+        mt = None if m is None else torch.tensor(m, dtype=torch.int32, device=self.device)
+        self._state_keep = (blob, mt)
+        _lib.check(self.lib.lbwn_gen_state_load(self._plan, self._ws.data_ptr(), blob.data_ptr(), state.n_streams,
+                                                _lib.ptr(mt), _lib.stream_ptr()))
+        return self
+
+    def fork(self, src):
+        """Continue several streams from one: an int sends every stream to the state of stream ``src``, a
+        list [batch_sz] is a gather (stream b continues from stream src[b]).  save_state + load_state."""
+        if self._plan is None:
+            raise ValueError('fork: no plan (build_graph and init_buffers first)')
+        if not isinstance(src, bool) and isinstance(src, (int, np.integer)):
+            src = [src] * self.batch_sz
+        m = self._check_map(src, self.batch_sz, 'fork')
+        if m is None:
+            raise ValueError('fork: src must be a stream index or a list of batch_sz indices')
+        return self.load_state(self.save_state(), m)
+
+    def _check_prefill(self, prefill, mel):
+        """prefill is False, True or 'fanout'; a fan-out takes a shared (2-D) mel only.  ValueError otherwise."""
+        if prefill not in (False, True, 'fanout'):
+            raise ValueError("prefill must be False, True or 'fanout', got %r" % (prefill,))
+        if prefill == 'fanout' and mel is not None and len(tuple(mel.shape)) != 2:
+            raise ValueError("prefill='fanout' takes a shared mel [n_frames, n_lc_in] only, got shape %s"
+                             % (tuple(mel.shape),))
+
+    def _fanout(self, gc_ids, mel):
+        """Prefill the teacher once per distinct voice in a private generator of that many streams (sharing
+        this one's parameters) and return (its state, the map stream -> record, n)."""
+        n = min(int(self.teacher_mu.numel()), self.max_steps)
+        if self.arch['n_gc_embed'] > 0:
+            ids = np.asarray(gc_ids, np.int32).reshape(-1)
+            voices, smap = np.unique(ids, return_inverse=True)
+        else:
+            voices, smap = None, np.zeros(self.batch_sz, np.int64)
+        nv = 1 if voices is None else len(voices)
+        if self._fan is None or self._fan[0] != (nv, n):
+            a = self.arch
+            sub = WaveNetGen(a['n_blocks'], a['n_block_layers'], a['n_quant'], a['n_res'], a['n_dil'], a['n_skip'],
+                             a['n_post'], a['n_gc_embed'], a['n_gc_category'], a['use_bias'], nv, self.chunk_sz, None,
+                             pre_bias=self.pre_bias, seed=self.seed, device=self.device, graph=False,
+                             n_lc_in=a['n_lc_in'], n_lc_out=a['n_lc_out'],
+                             lc_upsample=a['lc_upsample'] if a['n_lc_out'] > 0 else ())
+            sub.flat = self.flat          # the same parameters, not a copy
+            sub.vars = self.vars
+            sub.build_graph(n)
+            self._fan = ((nv, n), sub)
+        sub = self._fan[1]
+        sub.init_buffers(None if voices is None else voices, mel)
+        sub.prefill(self.teacher_mu.reshape(-1)[:n])
+        return sub.save_state(), [int(v) for v in smap.reshape(-1)], n
+
     def init_buffers(self, gc_ids=None, mel=None, prefill=False):
         """imodel.init_buffers: zero the lookback/loop buffers, load teacher + GC ids (+ the mel of
         an LC arch, upsampled once).  ``prefill=True`` with a teacher: start without the teacher
         vector and prefill its µ-law codes instead (at most max_steps of them); returns the number
         of steps already taken that way (0 otherwise); on an LC arch the prefilled steps are
-        conditioned on the mel this call loads."""
+        conditioned on the mel this call loads.  ``prefill='fanout'``: the same result for a teacher
+        shared by the streams, but the prompt is prefilled once per distinct voice id of ``gc_ids`` (once on
+        an arch without GC) and that state loaded into every stream of the voice; mel absent or 2-D."""
+        self._check_prefill(prefill, mel)
         if prefill and self.teacher_mu is not None:
             self._check_codes(self.teacher_mu, mel_coming=mel is not None)
+        mel_shared = mel
         mel = self._check_mel(mel)
         if mel is not None:   # frames past the plan's ceil(max_steps / hop) condition no step
             mel = mel[:, :-(-self.max_steps // self.hop)]
@@ -254,10 +438,20 @@ class WaveNetGen:
         self._mel = None      # lbwn_gen_start clears the loaded mel
         if mel is not None:
             if not isinstance(mel, torch.Tensor):
-                mel = torch.from_numpy(np.ascontiguousarray(mel, np.float32))
+                mel = torch.from_numpy(np.array(mel, np.float32))   # a writable copy (a broadcast view is not)
             self._mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
             _lib.check(self.lib.lbwn_gen_set_mel(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                                  self._mel.data_ptr(), self._mel.shape[1], _lib.stream_ptr()))
+        self._started = True
+        if prefill == 'fanout' and self.teacher_mu is not None:
+            state, smap, n = self._fanout(gc_ids, mel_shared)
+            self.load_state(state, smap)
+            # the outputs of the prefilled steps, as lbwn_gen_prefill leaves them: the prompt and its decode
+            from .ops import mu_decode
+            q = self.teacher_mu.reshape(-1)[:n].to(torch.int32).clamp(0, self.arch['n_quant'] - 1)
+            self.samples()[:, :n] = q
+            self.tensor('wav').view(self.batch_sz, self.max_steps)[:, :n] = mu_decode(q, self.arch['n_quant'])
+            return n
         if prefill and self.teacher_mu is not None:
             return self.prefill(self.teacher_mu.reshape(-1)[:self.max_steps])
         return 0
@@ -293,11 +487,14 @@ class WaveNetGen:
         fresh state; the returned waveform holds whole chunks only (imodel.py:256-258).  LC archs:
         mel must cover the run, gen_sz <= n_frames·hop + 1.  ``prefill=True``: the teacher's steps
         are prefilled in parallel instead of stepped (the same continuation up to fp32 rounding;
-        the waveform then starts with the µ-law-quantised teacher, not the model's ignored draws)."""
+        the waveform then starts with the µ-law-quantised teacher, not the model's ignored draws).
+        ``prefill='fanout'``: as True, the prompt prefilled once per distinct voice id (``init_buffers``)."""
+        self._check_prefill(prefill, mel)
+        mel_in = mel
         mel = self._check_mel(mel, int(gen_sz))
         if self._plan is None or self.max_steps < gen_sz:
             self.build_graph(gen_sz)
-        done = self.init_buffers(gc_ids, mel, prefill=prefill)
+        done = self.init_buffers(gc_ids, mel_in if prefill == 'fanout' else mel, prefill=prefill)
         self.step(max(int(gen_sz) - done, 0))
         self.check_status()
         n_out = (int(gen_sz) // self.chunk_sz) * self.chunk_sz
@@ -306,8 +503,11 @@ class WaveNetGen:
 
     def check_status(self):
         """Raise if a skip helper's granule poll timed out (status 5): the step's skip sum, and
-        every draw after it, would be wrong."""
+        every draw after it, would be wrong; or if the device refused a load_state (status 6: the
+        snapshot's header or the stream map does not fit the plan; nothing was loaded)."""
         s = int(self.tensor('status', torch.int32).item())
+        if s == 6:
+            raise RuntimeError('generation status 6: load_state refused the snapshot or the stream map')
         if s != 0:
             raise RuntimeError('generation status %d: a skip-helper hand-off timed out' % s)
 
