@@ -34,6 +34,7 @@ struct lbwn_plan {
   bool skip_ok = true;
   bool live_valid = false;   // the last forward wrote the lists
   bool dv_blk = false;     // the last backward exported DV k-blocked ([2L][m32(M)][32])
+  bool dz_blk = false;     // the last backward wrote dZ in chain order ([L·Cd/32][m32(M)·32])
   int head_colparts = 0;   // post2-bias column partial rows the last forward's head wrote (0: none)
   lbwn_arch a;
   int B, T, L, nbl, H, Cr, Cd, Cs, Cp, Q;
@@ -536,7 +537,8 @@ int lbwn_plan_tensor(const lbwn_plan* p, const char* name, size_t* off, size_t* 
   else if (!strcmp(name, "ctrace")) { *off = p->oCTRACE; *bytes = 8 * 2 * 16 * (size_t)p->a.n_blocks * p->a.n_block_layers; }
   else if (!strcmp(name, "dh")) { *off = p->oDH; *bytes = f * M * p->Cp; }
   else if (!strcmp(name, "ds")) { *off = p->oDS; *bytes = f * M * p->Cs; }
-  else if (!strcmp(name, "dz")) { *off = p->oDZ; *bytes = f * M * p->L * p->Cd; }
+  // rows [M][L·Cd], or after a bf16-split chain backward in chain order: whole 32-row blocks
+  else if (!strcmp(name, "dz")) { *off = p->oDZ; *bytes = f * (p->dz_blk ? (size_t)m32(p->M) : M) * p->L * p->Cd; }
   // the masked-position live lists (int32), valid after a forward that wrote them (bf16-split chain
   // plans without LBWN_SKIP_MASKED=0): klive's first nklive[0] entries
   else if (!strcmp(name, "tlive")) { *off = p->oLIVE; *bytes = 4 * ((M + 255) / 256); }
@@ -1100,6 +1102,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   g.A = DS; g.lda = Cs; g.B = P->skip; g.ldb = Cs; g.C = DZ; g.ldc = ldz; g.M = (int)M; g.N = (int)ldz; g.K = Cs;
   g.b3 = w3(p, ws, W3_SKIP_B);
   if (dz_chain) g.c_chain_ls = m32(M) * 32;
+  p->dz_blk = dz_chain;
   g.xcd2d = p->dz_xcd2d;
   g.row_live = row_live(g);
   Probe(p, st, "dz");

@@ -390,10 +390,14 @@ def loss_fcn(arch, P, logits, wav_q, ids, l2_factor):
     return stats, dlog
 
 
-def backward(arch, P, cache, dlogits, l2_factor):
+def backward(arch, P, cache, dlogits, l2_factor, intermediates=False):
     """Reverse-mode derivative of tmodel's total loss (TF autodiff restated,
     tmodel.py:354-358).  Returns {name: grad} for every trainable parameter,
-    including the l2_factor·θ term for non-BIAS vars."""
+    including the l2_factor·θ term for non-BIAS vars.  ``intermediates`` leaves in
+    cache['bwd'] what the tests need to name the kernel behind a wrong gradient: dh1 [B,T,Cp],
+    dS [B,T,Cs], per layer dz (full), dz_skip (its dS·SKIPᵀ term) [B,T,Cd] and dv
+    [B,T,2Cd] (signal | gate), dx0 (the gradient into the first layer's input) and, for GC
+    archs, gcd [n_cat+1, L·2Cd]: dv summed per voice id, layer l at columns l·2Cd."""
     ub = arch['use_bias']
     L = n_layers(arch)
     g = OrderedDict((k, np.zeros_like(v)) for k, v in P.items())
@@ -410,6 +414,13 @@ def backward(arch, P, cache, dlogits, l2_factor):
     emb, lc = cache['emb'], cache['lc']
     demb = np.zeros_like(emb) if emb is not None else None
     dlc = np.zeros_like(lc) if lc is not None else None
+    Cd = arch['n_dil']
+    bwd = None
+    if intermediates:
+        bwd = {'dh1': dh1, 'dS': dS, 'dz': [None] * L, 'dz_skip': [None] * L, 'dv': [None] * L, 'gcd': None}
+        if emb is not None:
+            bwd['gcd'] = np.zeros((P['GC_EMBED'].shape[0], L * 2 * Cd), dS.dtype)
+        cache['bwd'] = bwd
     for l in reversed(range(L)):
         b, bl, d = layer_index(arch, l)
         sfx = '_%d_%d' % (b, bl)
@@ -420,8 +431,14 @@ def backward(arch, P, cache, dlogits, l2_factor):
         if ub:
             g['SKIP_BIAS' + sfx] += dS.sum(axis=(0, 1))
             g['RESIDUAL_BIAS' + sfx] += dx.sum(axis=(0, 1))
-        dz = dS @ P['SKIP' + sfx].T + dx @ P['RESIDUAL' + sfx].T
+        dz_skip = dS @ P['SKIP' + sfx].T
+        dz = dz_skip + dx @ P['RESIDUAL' + sfx].T
         dv = {'SIGNAL': dz * sg * (1 - th * th), 'GATE': dz * th * sg * (1 - sg)}
+        if bwd is not None:
+            bwd['dz'][l], bwd['dz_skip'][l] = dz, dz_skip
+            bwd['dv'][l] = np.concatenate([dv['SIGNAL'], dv['GATE']], axis=2)
+        if bwd is not None and emb is not None:
+            np.add.at(bwd['gcd'][:, l * 2 * Cd:(l + 1) * 2 * Cd], cache['ids'], bwd['dv'][l])
         dprev = np.zeros_like(x)
         dcur = np.zeros_like(x)
         for nm in ('SIGNAL', 'GATE'):
@@ -444,6 +461,8 @@ def backward(arch, P, cache, dlogits, l2_factor):
         if d < dx.shape[1]:
             dxn[:, :-d] += dprev[:, d:]                    # gradient into SAVE is dropped
         dx = dxn
+    if bwd is not None:
+        bwd['dx0'] = dx
     np.add.at(g['PRE'], cache['wav_q'], dx)
     if ub:
         g['PRE_BIAS'] += dx.sum(axis=(0, 1))

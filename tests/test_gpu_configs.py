@@ -4,7 +4,8 @@ tmodel.py:68-83, :150-160, par/arch5.json:2-15) and arch1 (n_post1 key, GC 17/37
 par/arch1.json:2-10), forward + loss + backward against the float64 oracle.
 
 Bars as tests/test_gpu_parity.py: z within 1e-5 absolute on identical inputs (north_star),
-5e-5 end to end through 50 layers, SAVE 1e-5, n_valid exact, gradients 2e-4 of scale."""
+5e-5 end to end through 50 layers, SAVE 1e-5, n_valid exact, gradients 2e-4 of each tensor's
+own max (tests/gradcheck.py)."""
 import os
 
 import numpy as np
@@ -14,7 +15,8 @@ import torch
 from lbwn.arch import load_arch
 from oracle import wavenet_ref as R
 from tests.conftest import ROOT
-from tests.test_gpu_parity import close, make_net, oracle_params
+from tests.gradcheck import Worst
+from tests.test_gpu_parity import check_grads, close, make_net, oracle_params
 
 pytestmark = pytest.mark.gpu
 
@@ -63,20 +65,25 @@ def _check_config(arch, B, T, seed=0, grads=True, z_identical=True):
     np.testing.assert_allclose(stats[0] / st['n_valid'], st['mean_xent'], rtol=1e-5)
     for k, v in new_save.items():
         close(net.save_vars[k].cpu().numpy(), v, 1e-5, k)
-    if grads:
-        G = R.backward(arch, P, cache, dlog, 0.0)
-        inv = 1.0 / st['n_valid']
-        for name in net.layout.names():
-            close(net.grads[name].cpu().double().numpy() * inv, G[name], 2e-4, name)
-    if not z_identical:
-        return
-    # fresh forward from the original SAVE: every layer's z on identical inputs (the GPU's own
-    # x_l, halo = SAVE; GC rows and the upsampled LC from the oracle), then end to end
+    # fresh forward from the original SAVE (bit-reproducible: its s / r2 carry the relu signs the
+    # backward above saw): the skip sum and r2, then every gradient
     net2 = make_net(arch, B, seed=seed)
     net2.forward(q, mel, ids, backward=False)
     torch.cuda.synchronize()
     L, Cd, Cr = R.n_layers(arch), arch['n_dil'], arch['n_res']
     H, M = 2 ** (arch['n_block_layers'] - 1), B * T
+    s = net2.plan_tensor(T, 's').view(M, -1)[:, :arch['n_skip']].cpu().numpy()
+    close(s, cache['S'].reshape(M, -1), 1e-5, 'skip sum')
+    r2 = net2.plan_tensor(T, 'r2').view(M, -1)[:, :arch['n_post']].cpu().numpy()
+    close(r2, cache['r2'].reshape(M, -1), 2e-5, 'relu2')
+    if grads:
+        worst = Worst()
+        adopted = check_grads(net, arch, P, cache, dlog, st['n_valid'], s, r2, worst, intermediates=False)
+        worst.report('B=%d T=%d seed %d (relu ties adopted: %d of S, %d of h1)' % ((B, T, seed) + adopted))
+    if not z_identical:
+        return
+    # every layer's z on identical inputs (the GPU's own x_l, halo = SAVE; GC rows and the
+    # upsampled LC from the oracle), then end to end
     z = net2.plan_tensor(T, 'z').view(M, L * Cd).cpu().numpy()
     xs = net2.plan_tensor(T, 'x')
     stride = xs.numel() // L
@@ -97,8 +104,6 @@ def _check_config(arch, B, T, seed=0, grads=True, z_identical=True):
                                    err_msg='z layer %d (identical inputs)' % l)
         np.testing.assert_allclose(z[:, l * Cd:(l + 1) * Cd], cache['z'][l].reshape(M, Cd), rtol=0, atol=5e-5,
                                    err_msg='z layer %d (end to end)' % l)
-    s = net2.plan_tensor(T, 's').view(M, -1).cpu().numpy()
-    close(s, cache['S'].reshape(M, -1), 1e-5, 'skip sum')
 
 
 def test_arch5_deep_stack(chain_tile):

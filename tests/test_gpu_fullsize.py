@@ -8,22 +8,44 @@ graph, tmodel.py:354-358).  The numpy oracle pins this restatement at small size
 from the HIP path (lbwn_train_forward / lbwn_train_backward).
 
 Bars as tests/test_gpu_parity.py: z within 1e-5 on identical inputs (north_star), 5e-5 end to end,
-SAVE 1e-5, n_valid exact, mean xent 1e-5, gradients 2e-4 of scale."""
+SAVE 1e-5, n_valid exact, mean xent 1e-5, gradients 2e-4 of each tensor's own max
+(tests/gradcheck.py), the restatement taking the HIP forward's sign for the relu inputs within the
+forward bars of zero."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import wavenet_ref as R
+from tests.gradcheck import ADOPT_CAP, H1_TIE, S_TIE, Worst, grad_close, group_of
 from tests.test_gpu_configs import _arch, _batch
 from tests.test_gpu_parity import close, make_net, oracle_params
 
 pytestmark = pytest.mark.gpu
 
 
-def torch_forward(arch, P, q, ids, S, mel, keep_x=False):
+def relu_adopting(x, gpu, tie, name, adopted):
+    """relu(x), or with ``gpu`` (the HIP path's value of the relu's input or output, same
+    elements) x times a mask that takes the HIP path's sign where |x| is within ``tie`` of scale
+    of zero (tests/gradcheck.py adopt_relu_signs: the forward bars pin every other sign).  The
+    count goes to adopted[name] and is capped at 0.05 % of the elements."""
+    if gpu is None:
+        return torch.relu(x)
+    xd = x.detach()
+    bar = tie * max(1.0, float(xd.abs().max()))
+    gpu = gpu.reshape(xd.shape)
+    err = float((torch.relu(xd) - torch.relu(gpu)).abs().max())
+    assert err <= bar, 'relu(%s) forward: max err %.3g > %.3g' % (name, err, bar)
+    amb = xd.abs() <= bar
+    adopted[name] = int(amb.sum())
+    assert adopted[name] <= ADOPT_CAP * xd.numel(), 'relu ties in %s: %d of %d' % (name, adopted[name], xd.numel())
+    return x * torch.where(amb, gpu > 0, xd > 0)
+
+
+def torch_forward(arch, P, q, ids, S, mel, keep_x=False, gpu_s=None, gpu_r2=None, adopted=None):
     """oracle/wavenet_ref.py forward (tmodel.py:292-327) in float64 torch; P, S: {name: tensor}
     (requires_grad where gradients are wanted).  Returns logits [B,T,Q], the per-layer z, the
-    skip sum, the new SAVE rows and (keep_x) each layer's input x."""
+    skip sum, the new SAVE rows and (keep_x) each layer's input x.  gpu_s / gpu_r2: the HIP
+    forward's skip sum and r2, whose signs the two relus adopt at ties (relu_adopting)."""
     B, T = q.shape
     L = R.n_layers(arch)
     ub = arch['use_bias']
@@ -67,10 +89,10 @@ def torch_forward(arch, P, q, ids, S, mel, keep_x=False):
             xs.append(x.detach())
         Ssum = Ssum + skp
         x = x + res
-    h1 = torch.relu(Ssum) @ P['POST1']
+    h1 = relu_adopting(Ssum, gpu_s, S_TIE, 'S', adopted) @ P['POST1']
     if ub:
         h1 = h1 + P['POST1_BIAS']
-    logits = torch.relu(h1) @ P['POST2']
+    logits = relu_adopting(h1, gpu_r2, H1_TIE, 'h1', adopted) @ P['POST2']
     if ub:
         logits = logits + P['POST2_BIAS']
     return logits, zs, Ssum.detach(), new_save, xs
@@ -118,8 +140,11 @@ def test_restatement_matches_oracle():
     sx, nv = torch_sum_xent(tl, qt, it)
     assert nv == st['n_valid']
     (sx / nv).backward()
+    # float64 against float64, sums of a few thousand terms: 1e-10 of each tensor's own max is
+    # five orders above their rounding (and the absolute 1e-10 it replaces is kept beside it)
     for k, g in G.items():   # (the last layer's RESIDUAL feeds nothing: no autograd edge, zero gradient)
-        close(_grad(P[k]), g, 1e-10, k)
+        grad_close(_grad(P[k]), g, k, rel=1e-10)
+        np.testing.assert_allclose(_grad(P[k]), g, rtol=0, atol=1e-10, err_msg=k)
 
 
 @pytest.mark.parametrize('arch_name,B', [('arch5', 32), ('arch3', 8)])
@@ -143,23 +168,30 @@ def _full_size(arch_name, B):
     q, ids, mel = _batch(arch, B, T, 11)
     net = make_net(arch, B, seed=11)
     P0, S0, P, S, qt, it, mt = _tensors(net, q, ids, mel, 'cuda', True)
-    tl, zs, Ss, ns, _ = torch_forward(arch, P, qt, it, S, mt)
+    L, Cd, Cr = R.n_layers(arch), arch['n_dil'], arch['n_res']
+    H, M = 2 ** (arch['n_block_layers'] - 1), B * T
+
+    # the HIP forward first: its s / r2 give the restatement the signs of the relu inputs that lie
+    # within the forward bars of zero (about 5e-5 of the elements; a flipped mask moves a POST1 /
+    # SKIP column of the gradient, which is the function's property, not a kernel's error)
+    net.forward(q, mel, ids, backward=False)
+    torch.cuda.synchronize()
+    assert int(net.plan_tensor(T, 'status').view(torch.int32)[0]) == 0, 'chain hand-off timed out'
+    s = net.plan_tensor(T, 's').view(M, -1)[:, :arch['n_skip']].double()
+    r2 = net.plan_tensor(T, 'r2').view(M, -1)[:, :arch['n_post']].double()
+    adopted = {}
+    tl, zs, Ss, ns, _ = torch_forward(arch, P, qt, it, S, mt, gpu_s=s, gpu_r2=r2, adopted=adopted)
     sx, nv = torch_sum_xent(tl, qt, it)
     sx.backward()
     del tl
 
     # forward only: z on identical inputs (the plan's own layer inputs x_l, halo = SAVE, through
     # a float64 dilated conv + gate), z end to end, the skip sum, SAVE, n_valid, mean xent
-    net.forward(q, mel, ids, backward=False)
-    torch.cuda.synchronize()
-    assert int(net.plan_tensor(T, 'status').view(torch.int32)[0]) == 0, 'chain hand-off timed out'
     stats = net.stats.cpu().numpy()
     assert int(stats[1]) == nv
     np.testing.assert_allclose(stats[0] / nv, float(sx) / nv, rtol=1e-5)
     for k, v in ns.items():
         close(net.save_vars[k].cpu().numpy(), v.cpu().numpy(), 1e-5, k)
-    L, Cd, Cr = R.n_layers(arch), arch['n_dil'], arch['n_res']
-    H, M = 2 ** (arch['n_block_layers'] - 1), B * T
     z = net.plan_tensor(T, 'z').view(M, L * Cd).double()
     xall = net.plan_tensor(T, 'x')
     stride = xall.numel() // L
@@ -169,10 +201,10 @@ def _full_size(arch_name, B):
         lc = None
         if arch['n_lc_out'] > 0:
             lc = mt
-            for i, s in enumerate(arch['lc_upsample']):
+            for i, s_ in enumerate(arch['lc_upsample']):
                 F = Pd['LC_UPSAMPLE_%d' % i]
                 b_, t_, _ = lc.shape
-                lc = torch.einsum('bti,joi->btjo', lc, F).reshape(b_, t_ * s, F.shape[1])
+                lc = torch.einsum('bti,joi->btjo', lc, F).reshape(b_, t_ * s_, F.shape[1])
         for l in range(L):
             b, bl, d = R.layer_index(arch, l)
             sfx = '_%d_%d' % (b, bl)
@@ -191,9 +223,8 @@ def _full_size(arch_name, B):
             e2 = float((zg - zs[l].reshape(M, Cd)).abs().max())
             assert e1 <= 1e-5, 'z layer %d (identical inputs): %.3g' % (l, e1)
             assert e2 <= 5e-5, 'z layer %d (end to end): %.3g' % (l, e2)
-        s = net.plan_tensor(T, 's').view(M, -1).double()
         close(s.cpu().numpy(), Ss.reshape(M, -1).cpu().numpy(), 1e-5, 'skip sum')
-    del net, z, xall, s
+    del net, z, xall, s, r2
 
     # forward + backward from the same initial state: every gradient of the summed xent
     net = make_net(arch, B, seed=11)
@@ -201,5 +232,8 @@ def _full_size(arch_name, B):
     torch.cuda.synchronize()
     assert int(net.plan_tensor(T, 'status').view(torch.int32)[0]) == 0, 'chain hand-off timed out'
     scale = 1.0 / nv
+    worst = Worst()
     for name in net.layout.names():
-        close(net.grads[name].double().cpu().numpy() * scale, _grad(P[name]) * scale, 2e-4, name)
+        ours = net.grads[name].double().cpu().numpy() * scale
+        worst.add(group_of(name), grad_close(ours, _grad(P[name]) * scale, name))
+    worst.report('%s B=%d T=%d (relu ties adopted: %d of S, %d of h1)' % (arch_name, B, T, adopted['S'], adopted['h1']))
