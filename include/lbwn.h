@@ -73,6 +73,15 @@ size_t lbwn_plan_workspace_bytes(const lbwn_plan* plan);
  * or after a bf16-split chain backward k-blocked [2L][ceil(M/32)·32][32], the size reported
  * accordingly), "gctab"/"gcd" [n_cat+1][L·2·n_dil] (GC table, its gradient).  */
 int lbwn_plan_tensor(const lbwn_plan* plan, const char* name, size_t* offset, size_t* bytes);
+/* Which branch of the conditioning dispatch the plan takes (host fields, no device work; added after
+ * ABI 5 was declared, same ABI).  Keys: "up_fused" / "up_fused_bwd" (the LC upsample runs as one
+ * fused launch forward / backward, else one GEMM per stage), "lc_in_chain" (the plan carved the LC
+ * images: the bf16-split forward chain computes the LC term itself), "split_dlc", "split_dlcx",
+ * "split_dlct", "split_up0" .. "split_up7" (split-K counts of dLCcat, dlc, dLCcatᵀ and the per-stage
+ * filter gradients; 0 for a stage the arch does not have), and, valid after a backward, "dv_blk" (DV
+ * was exported k-blocked) and "dlc_parts" (split-K partials dlc left for the fused upsample backward).
+ * An unknown key is EINVAL. */
+int lbwn_plan_info(const lbwn_plan* plan, const char* key, int64_t* value);
 /* One-shot timing probe: the next lbwn_train_forward/backward on this plan records
  * hipEvent_t ev_start right before and ev_stop right after the named launch(es):
  * "layer_fwd" (the residual stack: the persistent chain launch, or the span of the
@@ -377,6 +386,43 @@ int lbwn_colpart_parts_abi(int M);
  * (row_live allowed); 2: k_live is allowed (both operands mn-contiguous assumed; only M, N, K are
  * read). */
 int lbwn_gemm_form_query(int which, int M, int N, int K, int a_kcontig, int presplit, int row_exact, int colpart);
+
+/* ---- the conditioning kernels on their own inputs (parity tests; added after ABI 5 was declared,
+ * same ABI: symbols added, none altered) ----
+ * LC upsample (tmodel.py:68-83): nup stages of conv1d_transpose with kernel = stride = strides[i],
+ * stage i maps rows [R_i][I_i] to [R_i·s_i][Lo] (R_0 = 1 per mel frame, I_0 = Li, later I_i = Lo):
+ * out[s·t + j][o] = Σ_c in[t][c]·F_i[j][o][c], F_i fp32 [s_i][Lo][I_i].  The fused kernels run one
+ * block per mel frame inside an envelope: 1..4 stages of stride 1..8, Li <= Lo, both multiples of 4,
+ * hop = Π s_i <= 256, and both kernels' LDS layouts within 40448 floats.
+ * lbwn_lc_upsample_fused_ok: 1 inside the envelope, else 0 (no device work).
+ * lbwn_lc_upsample_part_floats: floats of the backward's scratch dpart, frames·Σ_i s_i·Lo·I_i.
+ * lbwn_lc_upsample_forward: mel [frames][Li] -> act[i] [frames·R_{i+1}][Lo], every stage's output.
+ * lbwn_lc_upsample_backward: dF[i] = the filter gradients [s_i][Lo][I_i] (overwritten) given
+ *   d(act[nup-1]) = the sum of dlc_parts (>= 1) partials [frames·hop][Lo], dlc_stride floats apart
+ *   (a multiple of 4, >= frames·hop·Lo; unused for one part), the mel and the stage inputs
+ *   act[0 .. nup-2] (act[nup-1] is not read and may be NULL).  Per-frame partials go to dpart and are
+ *   summed in frame order (deterministic).
+ * Every pointer is device memory, 16-byte aligned; F, act and dF are host arrays of nup device
+ * pointers.  Outside the envelope both launches return EINVAL, naming the envelope, before any launch. */
+int lbwn_lc_upsample_fused_ok(int nup, const int* strides, int Li, int Lo);
+int64_t lbwn_lc_upsample_part_floats(int nup, const int* strides, int Li, int Lo, int frames);
+int lbwn_lc_upsample_forward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                             const float* const* F, float* const* act, void* stream);
+int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                              const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                              int64_t dlc_stride, float* dpart, float* const* dF, void* stream);
+/* GC table and its gradients (tmodel.py:92-114, :150-154), with N = L·2·Cd and column
+ * n = l·2Cd + s·Cd + o (s = 0 signal, 1 gate), emb [ncat1][Ge], wsig / wgate [L][Ge][Cd]:
+ *   lbwn_gc_table: out[c][n] = Σ_e emb[c][e]·W_s[l][e][o], out [ncat1][N].
+ *   lbwn_gc_grads, from gcd [ncat1][N] = d(out): dsig / dgate [L][Ge][Cd], dW_s[l][e][o] =
+ *     Σ_c emb[c][e]·gcd[c][n], and demb[c][e] = Σ_n gcd[c][n]·W_s[l][e][o]; all three overwritten.
+ *     part: scratch of lbwn_gc_part_floats_abi(L, Ge, Cd) floats.
+ * Ge (n_gc_embed) must be in [1, 32], else EINVAL before any launch. */
+int lbwn_gc_table(const float* emb, const float* wsig, const float* wgate, float* out, int L, int ncat1, int Ge,
+                  int Cd, void* stream);
+int lbwn_gc_grads(const float* emb, const float* wsig, const float* wgate, const float* gcd, float* part,
+                  float* demb, float* dsig, float* dgate, int L, int ncat1, int Ge, int Cd, void* stream);
+int64_t lbwn_gc_part_floats_abi(int L, int Ge, int Cd);
 
 /* One residual layer forward (tmodel.py:117-184): x_in is the [B][H+T][n_res] halo
  * buffer whose rows [H-d, H) hold SAVE; writes z [M][*] (row stride ldz) and, if x_out,

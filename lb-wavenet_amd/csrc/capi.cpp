@@ -113,6 +113,84 @@ int lbwn_gemm_form_query(int which, int M, int N, int K, int a_kcontig, int pres
   return -1;
 }
 
+// ---- the conditioning kernels on their own inputs (cond.hip) ----
+int lbwn_lc_upsample_fused_ok(int nup, const int* strides, int Li, int Lo) {
+  if (!strides) return 0;
+  return lbwn_lc_up_fused_ok(nup, strides, Li, Lo) ? 1 : 0;
+}
+
+int64_t lbwn_lc_upsample_part_floats(int nup, const int* strides, int Li, int Lo, int frames) {
+  if (!strides || nup < 1 || nup > 8 || frames < 1) return 0;
+  int64_t tot = 0;
+  for (int i = 0; i < nup; ++i) tot += (int64_t)strides[i] * Lo * (i ? Lo : Li);
+  return tot * frames;
+}
+
+int lbwn_lc_upsample_forward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                             const float* const* F, float* const* act, void* stream) {
+  LBWN_REQUIRE(strides && mel && F && act, "lc_upsample_forward: null argument");
+  LBWN_REQUIRE(frames >= 1, "lc_upsample_forward: frames must be >= 1");
+  LBWN_REQUIRE(lbwn_lc_up_fused_ok(nup, strides, Li, Lo),
+               "lc_upsample_forward: shape outside the fused kernel's envelope");
+  LBWN_REQUIRE(((uintptr_t)mel & 15) == 0, "lc_upsample_forward: mel must be 16-byte aligned");
+  for (int i = 0; i < nup; ++i) {
+    LBWN_REQUIRE(F[i] && act[i], "lc_upsample_forward: F[%d] or act[%d] is null", i, i);
+    LBWN_REQUIRE((((uintptr_t)F[i] | (uintptr_t)act[i]) & 15) == 0,
+                 "lc_upsample_forward: F[%d], act[%d] must be 16-byte aligned", i, i);
+  }
+  LBWN_REQUIRE(lbwn_lc_upsample_part_floats(nup, strides, Li, Lo, frames) < (1ll << 31),
+               "lc_upsample_forward: too many frames");
+  return lbwn_lc_up_fwd_launch(nup, strides, Li, Lo, frames, mel, F, act, (hipStream_t)stream);
+}
+
+int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                              const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                              int64_t dlc_stride, float* dpart, float* const* dF, void* stream) {
+  LBWN_REQUIRE(strides && mel && F && act && dlc && dpart && dF, "lc_upsample_backward: null argument");
+  LBWN_REQUIRE(frames >= 1, "lc_upsample_backward: frames must be >= 1");
+  LBWN_REQUIRE(lbwn_lc_up_fused_ok(nup, strides, Li, Lo),
+               "lc_upsample_backward: shape outside the fused kernel's envelope");
+  for (int i = 0; i < nup; ++i) {
+    LBWN_REQUIRE(F[i] && dF[i], "lc_upsample_backward: F[%d] or dF[%d] is null", i, i);
+    LBWN_REQUIRE(i + 1 == nup || act[i], "lc_upsample_backward: act[%d] is null", i);
+    LBWN_REQUIRE((((uintptr_t)F[i] | (uintptr_t)dF[i] | (uintptr_t)act[i]) & 15) == 0,
+                 "lc_upsample_backward: F[%d], dF[%d], act[%d] must be 16-byte aligned", i, i, i);
+  }
+  LBWN_REQUIRE(lbwn_lc_upsample_part_floats(nup, strides, Li, Lo, frames) < (1ll << 31),
+               "lc_upsample_backward: too many frames");
+  int hop = 1;
+  for (int i = 0; i < nup; ++i) hop *= strides[i];
+  LBWN_REQUIRE(dlc_parts >= 1, "lc_upsample_backward: dlc_parts must be >= 1");
+  LBWN_REQUIRE(dlc_parts == 1 || (dlc_stride >= (int64_t)frames * hop * Lo && dlc_stride % 4 == 0),
+               "lc_upsample_backward: dlc_stride must be a multiple of 4 and >= frames*hop*Lo");
+  LBWN_REQUIRE((((uintptr_t)dlc | (uintptr_t)mel | (uintptr_t)dpart) & 15) == 0,
+               "lc_upsample_backward: mel, dlc and dpart must be 16-byte aligned");
+  float* a[4] = {nullptr, nullptr, nullptr, nullptr};   // read only by the backward
+  for (int i = 0; i < nup; ++i) a[i] = const_cast<float*>(act[i]);
+  return lbwn_lc_up_bwd_launch(nup, strides, Li, Lo, frames, mel, F, a, dlc, dpart, dF, (hipStream_t)stream, nullptr,
+                               nullptr, dlc_parts, (long)dlc_stride);
+}
+
+int lbwn_gc_table(const float* emb, const float* wsig, const float* wgate, float* out, int L, int ncat1, int Ge, int Cd,
+                  void* stream) {
+  LBWN_REQUIRE(emb && wsig && wgate && out, "gc_table: null argument");
+  LBWN_REQUIRE(L >= 1 && ncat1 >= 1 && Cd >= 1, "gc_table: L, ncat1 and Cd must be >= 1");
+  LBWN_REQUIRE(Ge >= 1 && Ge <= 32, "gc_table: n_gc_embed must be in [1, 32]");
+  return lbwn_gc_table_launch(emb, wsig, wgate, out, L, ncat1, Ge, Cd, (hipStream_t)stream);
+}
+
+int64_t lbwn_gc_part_floats_abi(int L, int Ge, int Cd) {
+  if (L < 1 || Ge < 1 || Cd < 1) return 0;
+  return (int64_t)lbwn_gc_part_floats(L, Ge, Cd);
+}
+
+int lbwn_gc_grads(const float* emb, const float* wsig, const float* wgate, const float* gcd, float* part, float* demb,
+                  float* dsig, float* dgate, int L, int ncat1, int Ge, int Cd, void* stream) {
+  LBWN_REQUIRE(emb && wsig && wgate && gcd && part && demb && dsig && dgate, "gc_grads: null argument");
+  LBWN_REQUIRE(L >= 1 && ncat1 >= 1 && Cd >= 1, "gc_grads: L, ncat1 and Cd must be >= 1");
+  return lbwn_gc_grad_launch(emb, wsig, wgate, gcd, part, demb, dsig, dgate, L, ncat1, Ge, Cd, (hipStream_t)stream);
+}
+
 int lbwn_gemm_set_mode(int mode) { return lbwn_gemm_set_mode_impl(mode); }
 int lbwn_gemm_get_mode(void) { return lbwn_gemm_mode(); }
 

@@ -557,6 +557,23 @@ int lbwn_plan_tensor(const lbwn_plan* p, const char* name, size_t* off, size_t* 
 }
 size_t lbwn_plan_workspace_bytes(const lbwn_plan* p) { return p ? p->total : 0; }
 
+// which branch of the conditioning dispatch this plan takes (host fields; no device work)
+int lbwn_plan_info(const lbwn_plan* p, const char* key, int64_t* value) {
+  LBWN_REQUIRE(p && key && value, "plan_info: null argument");
+  if (!strcmp(key, "up_fused")) *value = p->up_fused;
+  else if (!strcmp(key, "up_fused_bwd")) *value = p->up_fused_bwd;
+  else if (!strcmp(key, "lc_in_chain")) *value = p->oLCX != 0 && p->chain;
+  else if (!strcmp(key, "split_dlc")) *value = p->split_dlc;
+  else if (!strcmp(key, "split_dlcx")) *value = p->split_dlcx;
+  else if (!strcmp(key, "split_dlct")) *value = p->split_dlct;
+  else if (!strncmp(key, "split_up", 8) && key[8] >= '0' && key[8] <= '7' && !key[9])
+    *value = p->split_up[key[8] - '0'];
+  else if (!strcmp(key, "dv_blk")) *value = p->dv_blk;         // of the last backward
+  else if (!strcmp(key, "dlc_parts")) *value = p->dlc_parts;   // of the last backward
+  else LBWN_REQUIRE(false, "plan_info: unknown key '%s'", key);
+  return 0;
+}
+
 // the masked-position live lists (lbwn_plan::oLIVE)
 static int* live_t(const lbwn_plan* p, void* ws) { return reinterpret_cast<int*>(static_cast<char*>(ws) + p->oLIVE); }
 static int* live_k(const lbwn_plan* p, void* ws) { return live_t(p, ws) + (p->M + 255) / 256; }

@@ -100,6 +100,18 @@ _SIGS = {
     'lbwn_gemm_mbits_words_abi': (c_int64, [c_int, c_int]),
     'lbwn_colpart_parts_abi': (c_int, [c_int]),
     'lbwn_gemm_form_query': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'lbwn_plan_info': (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_int64)]),
+    # (nup, strides, Li, Lo[, frames]); F / act / dF are host arrays of device pointers
+    'lbwn_lc_upsample_fused_ok': (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int]),
+    'lbwn_lc_upsample_part_floats': (c_int64, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int]),
+    'lbwn_lc_upsample_forward': (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_fp,
+                                         ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), c_void_p]),
+    'lbwn_lc_upsample_backward': (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_fp,
+                                          ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), c_fp, c_int, c_int64, c_fp,
+                                          ctypes.POINTER(c_fp), c_void_p]),
+    'lbwn_gc_table': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_void_p]),
+    'lbwn_gc_grads': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_void_p]),
+    'lbwn_gc_part_floats_abi': (c_int64, [c_int, c_int, c_int]),
     'lbwn_gemm_set_mode': (c_int, [c_int]),
     'lbwn_gemm_get_mode': (c_int, []),
     'lbwn_layer_image_floats_abi': (c_int, []),

@@ -167,6 +167,12 @@ class WaveNetTrain:
         _lib.check(self.lib.lbwn_plan_tensor(h, name.encode(), ctypes.byref(off), ctypes.byref(nb)))
         return self._ws[off.value:off.value + nb.value].view(torch.float32)
 
+    def plan_info(self, T, key):
+        """A dispatch fact of the plan (lbwn_plan_info: 'up_fused', 'split_dlcx', 'dlc_parts', ...)."""
+        v = _lib.c_int64()
+        _lib.check(self.lib.lbwn_plan_info(self._plan(T), key.encode(), ctypes.byref(v)))
+        return v.value
+
     def workspace_bytes(self, T):
         self._plan(T)
         return self._plans[T][1]

@@ -97,11 +97,11 @@ def small_arch(nb=2, nbl=4, Cr=32, Cd=32, Cs=64, Cp=32, Q=256):
                                n_post=Cp, n_gc_embed=0, n_gc_category=0, use_bias=True))
 
 
-def cond_arch(gc, lc, C=32):
-    a = dict(n_blocks=1, n_block_layers=4, n_quant=256, n_res=C, n_dil=C, n_skip=64, n_post=32,
-             n_gc_embed=8 if gc else 0, n_gc_category=5 if gc else 0, use_bias=True)
+def cond_arch(gc, lc, C=32, Li=12, Lo=16, strides=(2, 4), n_blocks=1, n_block_layers=4, Ge=8, ncat=5):
+    a = dict(n_blocks=n_blocks, n_block_layers=n_block_layers, n_quant=256, n_res=C, n_dil=C, n_skip=64, n_post=32,
+             n_gc_embed=Ge if gc else 0, n_gc_category=ncat if gc else 0, use_bias=True)
     if lc:
-        a.update(n_lc_in=12, n_lc_out=16, lc_upsample=[2, 4])
+        a.update(n_lc_in=Li, n_lc_out=Lo, lc_upsample=list(strides))
     return normalize_arch(a)
 
 

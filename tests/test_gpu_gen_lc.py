@@ -168,6 +168,30 @@ def test_gen_lc_small_free_running_ragged(form, monkeypatch):
     np.testing.assert_allclose(lc, lc_ref, rtol=0, atol=1e-5 * np.abs(lc_ref).max())
 
 
+def test_gen_lc_upsample_gemm_fallback(lib, monkeypatch):
+    """n_lc_in 24 > n_lc_out 16 is outside the fused upsample's envelope (Li > Lo), so
+    lbwn_gen_set_mel runs the upsample as one GEMM per stage: the plan's "lc" against
+    lc_upsample_fwd in float64 at 1e-5 of max(1, max), and the 17 steps drawn from it."""
+    import ctypes
+    monkeypatch.delenv('LBWN_GEN_PERSIST', raising=False)
+    monkeypatch.delenv('LBWN_GEN_LC_CHUNK', raising=False)
+    arch = normalize_arch(dict(small(), n_lc_in=24))
+    assert lib.lbwn_lc_upsample_fused_ok(2, (ctypes.c_int * 2)(2, 4), 24, 16) == 0
+    B, frames = 3, 2
+    n = frames * 8 + 1
+    mel = np.random.default_rng(16).standard_normal((B, frames, 24)).astype(np.float32)
+    g, P = make_gen(arch, B, chunk=10)
+    g.run(n, mel=mel)
+    torch.cuda.synchronize()
+    lc_ref, _ = R.lc_upsample_fwd(arch, P, mel.astype(np.float64))
+    lc = g.tensor('lc')[:B * frames * 8 * 16].view(B, frames * 8, 16).cpu().numpy()
+    err, bar = np.abs(lc - lc_ref).max(), 1e-5 * max(1.0, np.abs(lc_ref).max())
+    print('lc (per-stage GEMMs): max err %.3e (bar %.3e)' % (err, bar))
+    assert np.isfinite(lc).all() and err <= bar, (err, bar)
+    got = g.samples().cpu().numpy()[:, :n]
+    check_run(g, oracle_logits(arch, P, got, mel), n)
+
+
 def test_gen_lc_gc_teacher_forced(form):
     """LC + GC (8 / 5 voices), teacher-forced over the first 25 steps, then free; default NC."""
     arch = small(gc=5)

@@ -518,9 +518,11 @@ def test_plan_conditioning_ragged(chain_tile):
     check_conditioning(1, 1, 32, 3, 136, chain_tile)
 
 
-def check_conditioning(gc, lc, C, B, T, chain_tile):
-    arch = cond_arch(gc, lc, C)
-    net = make_net(arch, B)
+def check_conditioning(gc, lc, C, B, T, chain_tile, arch=None, seed=0):
+    """arch: another conditioned arch than cond_arch(gc, lc, C) (tests/test_gpu_cond_plan.py); seed:
+    of the parameters.  Returns the net after its backward (its plan_info is then complete)."""
+    arch = arch or cond_arch(gc, lc, C)
+    net = make_net(arch, B, seed=seed)
     q, ids, mel = cond_batch(arch, B, T)
     P, S = oracle_params(net)
     lg, cache, new_save = R.forward(arch, P, q, ids, S, mel=mel)
@@ -537,7 +539,7 @@ def check_conditioning(gc, lc, C, B, T, chain_tile):
     assert any(n.startswith('GC_') for n in names) == bool(gc)
     assert any(n.startswith('LC_') for n in names) == bool(lc)
     # the signs of the relu inputs: a fresh forward-only plan (bit-reproducible) keeps s / r2
-    net2 = make_net(arch, B)
+    net2 = make_net(arch, B, seed=seed)
     net2.forward(q, mel, ids, backward=False)
     torch.cuda.synchronize()
     M = B * T
@@ -550,6 +552,7 @@ def check_conditioning(gc, lc, C, B, T, chain_tile):
     check_bwd_intermediates(net, arch, B, T, cache, dlog, st['n_valid'], worst)
     worst.report('cond_arch(%d, %d, %d) B=%d T=%d %s (relu ties adopted: %d of S, %d of h1)'
                  % ((gc, lc, C, B, T, chain_tile) + adopted))
+    return net
 
 
 def test_staged_equals_unstaged_bitwise():
