@@ -603,9 +603,14 @@ int lbwn_pre_grad_ws_floats(int Q, int Cr) { return PG_BLOCKS * (Q * Cr + Cr); }
 
 int lbwn_pre_grad_launch(const int* q, const float* g, const float* dprev, int gd, int B, int T, int Cr, int Q,
                          float* dpre, float* dpre_b, float* ws, hipStream_t st) {
-  LBWN_REQUIRE(Cr >= 1 && Cr <= 32 && Q >= 1 && Q * 32 * 4 <= 65536, "pre_grad: Cr <= 32 and Q <= 512 required");
+  // the histogram is Q rows of 32 floats: up to 64 KB (Q <= 512) as ever; a wider head (the plan takes
+  // any n_quant) asks for a larger dynamic LDS block, up to 128 KB of the CU's 160
+  LBWN_REQUIRE(Cr >= 1 && Cr <= 32 && Q >= 1 && Q <= 1024, "pre_grad: Cr <= 32 and Q <= 1024 required");
   LBWN_REQUIRE((long)B * T * Cr < (1L << 31), "pre_grad: B*T*Cr must be < 2^31");
   const int nb = PG_BLOCKS, nw = 1;   // one-wave blocks (two-wave blocks wait for LDS)
+  if (nw * Q * 32 * 4 > 65536)
+    LBWN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pre_grad_part_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, nw * Q * 32 * 4));
   float* part = ws;
   float* bpart = ws + (long)PG_BLOCKS * Q * Cr;
   pre_grad_part_kernel<<<nb, 64 * nw, nw * Q * 32 * 4, st>>>(q, g, dprev, gd, B, T, Cr, Q, part, bpart);

@@ -21,11 +21,11 @@ POST2_SCALE = {256: 30.0, 100: 10.0, 300: 30.0}
 SEED = 7
 
 
-def small(Q=256, gc=0):
+def small(Q=256, gc=0, use_bias=True):
     """The small arch of tests/test_gpu_gen.py with n_quant = Q."""
     from lbwn.arch import normalize_arch
     return normalize_arch(dict(n_blocks=2, n_block_layers=4, n_quant=Q, n_res=32, n_dil=32, n_skip=64,
-                               n_post=32, n_gc_embed=8 if gc else 0, n_gc_category=gc, use_bias=True))
+                               n_post=32, n_gc_embed=8 if gc else 0, n_gc_category=gc, use_bias=use_bias))
 
 
 _PARAMS = {}

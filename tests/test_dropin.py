@@ -18,9 +18,9 @@ from lbwn.tmodel import WaveNetTrain
 from tests.conftest import ROOT
 
 
-def small_arch():
+def small_arch(use_bias=True):
     return normalize_arch(dict(n_blocks=1, n_block_layers=3, n_quant=256, n_res=8, n_dil=8, n_skip=16, n_post=8,
-                               n_gc_embed=0, n_gc_category=0, use_bias=True))
+                               n_gc_embed=0, n_gc_category=0, use_bias=use_bias))
 
 
 def test_checkpoint_roundtrip_reference_names(tmp_path):
@@ -46,6 +46,42 @@ def test_checkpoint_roundtrip_reference_names(tmp_path):
     assert torch.equal(a.flat, b.flat) and torch.equal(a.save_flat, b.save_flat)
     assert torch.equal(a.counters[:3], b.counters[:3]) and b.global_step_host == 17
     assert all(torch.equal(x, y) for x, y in zip(opt.slots(a), opt2.slots(b)))
+
+
+@pytest.mark.parametrize('use_bias', [True, False])
+def test_checkpoint_roundtrip_exact_names(tmp_path, use_bias):
+    """save -> restore with and without biases: the file holds exactly the layout's tensors, SAVE, the
+    counters and the Adam slots of the layout's tensors -- no missing name and no extra one -- and a
+    net of the other use_bias refuses it (with: names missing; without: nothing to load them into)."""
+    arch = dict(load_arch(os.path.join(ROOT, 'par', 'arch5.json')), use_bias=use_bias, n_blocks=1, n_block_layers=3)
+    mk = lambda step, seed, a=arch: WaveNetTrain(**a, batch_sz=2, l2_factor=1e-3, device='cpu',   # noqa: E731
+                                                 ckpt_path=str(tmp_path / 'run.net'), resume_step=step, seed=seed)
+    a = mk(0, 3)
+    a.init_vars(3, bias_scale=0.1)
+    opt = AdamOptimizer()
+    m, v = opt.slots(a)
+    m.uniform_(-1, 1)
+    v.uniform_(0, 1)
+    a.counters[:3] = torch.tensor([17, 12345, 16])
+    t = load_tensors(a.save(17, opt))
+    names = a.layout.names()
+    assert any('BIAS' in n for n in names) == use_bias
+    want = (set(names) | set(a.save_vars) | {'GLOBAL_STEP', 'VALID_SAMPLES', 'Adam/step'}
+            | {n + sfx for n in names for sfx in ('/Adam', '/Adam_1')})
+    assert set(t) == want, (sorted(set(t) - want)[:4], sorted(want - set(t))[:4])
+    b = mk(17, 9)
+    opt2 = AdamOptimizer()
+    loaded = b.restore(opt2)
+    assert set(loaded) == want
+    assert torch.equal(a.flat, b.flat) and torch.equal(a.save_flat, b.save_flat)
+    assert torch.equal(a.counters[:3], b.counters[:3]) and b.global_step_host == 17
+    assert all(torch.equal(x, y) for x, y in zip(opt.slots(a), opt2.slots(b)))
+    other = mk(17, 9, dict(arch, use_bias=not use_bias))
+    if use_bias:      # the no-bias net finds every tensor it has; the file's bias tensors are extra names
+        assert set(other.state_tensors()) < set(t)
+    else:             # the with-bias net lacks its biases in the file
+        with pytest.raises(SystemExit):
+            other.restore()
 
 
 def test_checkpoint_rotation_and_missing(tmp_path):

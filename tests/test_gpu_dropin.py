@@ -35,10 +35,19 @@ def _dataset(tmp_path, n_files=6, voices=3):
 
 
 def test_train_resume_generate(tmp_path, capsys):
+    _train_resume_generate(tmp_path, capsys, True)
+
+
+def test_train_resume_generate_no_bias(tmp_path, capsys):
+    """The same run on the arch with use_bias = false: no *_BIAS tensor in any checkpoint."""
+    _train_resume_generate(tmp_path, capsys, False)
+
+
+def _train_resume_generate(tmp_path, capsys, use_bias):
     import generate
     import train
     arch = dict(n_blocks=1, n_block_layers=4, n_quant=256, n_res=32, n_dil=32, n_skip=64, n_post=32,
-                n_gc_embed=8, n_gc_category=3, n_lc_in=0, n_lc_out=0, lc_upsample=[], use_bias=True,
+                n_gc_embed=8, n_gc_category=3, n_lc_in=0, n_lc_out=0, lc_upsample=[], use_bias=use_bias,
                 wav_input_type='mu_law_quant')
     par = dict(batch_sz=2, sample_rate=16000, slice_sz=128, l2_factor=1e-3, learning_rate=1e-3, prefetch_sz=4,
                add_summary=False, n_keep_checkpoints=3, n_valid_total=100000)
@@ -59,6 +68,7 @@ def test_train_resume_generate(tmp_path, capsys):
         assert os.path.exists(ckpt_file(pfx + '.net', s)) and os.path.exists(ckpt_file(pfx + '.dset', s))
     t = load_tensors(pfx + '.net-4')
     assert int(t['GLOBAL_STEP'][0]) == 4
+    assert any('BIAS' in n for n in t) == use_bias and any('BIAS' in n for n in net.vars) == use_bias
     np.testing.assert_array_equal(t['SIGNAL_0_3'].numpy(), net.vars['SIGNAL_0_3'].cpu().numpy())
     # resume from step 4 and take two more steps
     net2 = train.main(['--max-steps', '7', '--resume-step', '4', '--save-interval', '2', pfx, str(af), str(pf), cat])

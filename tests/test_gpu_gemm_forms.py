@@ -685,12 +685,13 @@ def test_refused_struct_size(lib):
 # ---- head widths that are no multiple of 32, through whole plans ------------------------------
 
 @pytest.mark.parametrize('Cs,Cp,Q,B,T', [(200, 100, 100, 2, 200), (200, 100, 100, 2, 4096), (136, 72, 260, 2, 200),
-                                         (640, 96, 256, 2, 200)])
+                                         (640, 96, 256, 2, 200), (64, 32, 520, 2, 200)])
 def test_plan_odd_head_widths(lib, Cs, Cp, Q, B, T):
     """lbwn_plan_create takes any n_skip / n_post / n_quant (padded to 4): forward, SAVE, every
     gradient and every layer's z against the float64 oracle at widths that leave ragged column
     tiles in every head GEMM (136 = 128 + 8, 200, 100 and 72 below one tile, 96 and 640 = the
-    96- and 160-column forms, 260 past 256); B·T = 8192 runs the tall forms at ragged N."""
+    96- and 160-column forms, 260 past 256); B·T = 8192 runs the tall forms at ragged N; n_quant = 520
+    is the generic head kernel and a PRE gradient histogram past 64 KB of LDS."""
     check_plan(small_arch(nb=1, nbl=4, Cs=Cs, Cp=Cp, Q=Q), B, T)
 
 

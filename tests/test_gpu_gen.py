@@ -28,9 +28,9 @@ def form(request, monkeypatch):
     return request.param
 
 
-def small(gc=0):
+def small(gc=0, use_bias=True):
     return normalize_arch(dict(n_blocks=2, n_block_layers=4, n_quant=256, n_res=32, n_dil=32, n_skip=64,
-                               n_post=32, n_gc_embed=8 if gc else 0, n_gc_category=gc, use_bias=True))
+                               n_post=32, n_gc_embed=8 if gc else 0, n_gc_category=gc, use_bias=use_bias))
 
 
 def make_gen(arch, B, chunk, seed=7, teacher=None, pre_bias=True, graph=True):

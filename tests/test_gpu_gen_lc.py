@@ -37,10 +37,10 @@ def form(request, monkeypatch):
     return request.param
 
 
-def small(gc=0):
+def small(gc=0, use_bias=True):
     return normalize_arch(dict(n_blocks=2, n_block_layers=4, n_quant=256, n_res=32, n_dil=32, n_skip=64,
                                n_post=32, n_gc_embed=8 if gc else 0, n_gc_category=gc, n_lc_in=12, n_lc_out=16,
-                               lc_upsample=[2, 4], use_bias=True))
+                               lc_upsample=[2, 4], use_bias=use_bias))
 
 
 _PARAMS = {}
@@ -77,7 +77,8 @@ def _near_tie(lg_row, u, tol=5e-5):
 def step0(arch, P, B, gc, lc_row):
     """Generation step 0 in float64: zero input (+ PRE_BIAS), zero lookback, LC row lc_row [B, Lo].
     Returns (SAVE with g_l in each layer's last row, logits [B, Q])."""
-    x = np.zeros((B, arch['n_res'])) + P['PRE_BIAS']
+    bias = (lambda n: P[n]) if arch['use_bias'] else (lambda n: 0.0)      # no-bias archs have no *_BIAS tensor
+    x = np.zeros((B, arch['n_res'])) + bias('PRE_BIAS')
     emb = P['GC_EMBED'][np.asarray(gc)] if arch['n_gc_embed'] > 0 else None
     save, S = {}, 0.0
     for l in range(R.n_layers(arch)):
@@ -86,13 +87,13 @@ def step0(arch, P, B, gc, lc_row):
         sv = np.zeros((B, d, arch['n_res']))
         sv[:, -1] = x
         save['SAVE_%d%s' % (d, sfx)] = sv
-        v = {nm: x @ P[nm + sfx][1] + P[nm + '_BIAS' + sfx] + lc_row @ P['LC_' + nm + sfx]
+        v = {nm: x @ P[nm + sfx][1] + bias(nm + '_BIAS' + sfx) + lc_row @ P['LC_' + nm + sfx]
              + (emb @ P['GC_' + nm + sfx] if emb is not None else 0.0) for nm in ('SIGNAL', 'GATE')}
         z = np.tanh(v['SIGNAL']) * R._sigmoid(v['GATE'])
-        S = S + z @ P['SKIP' + sfx] + P['SKIP_BIAS' + sfx]
-        x = x + z @ P['RESIDUAL' + sfx] + P['RESIDUAL_BIAS' + sfx]
-    h = np.maximum(np.maximum(S, 0) @ P['POST1'] + P['POST1_BIAS'], 0)
-    return save, h @ P['POST2'] + P['POST2_BIAS']
+        S = S + z @ P['SKIP' + sfx] + bias('SKIP_BIAS' + sfx)
+        x = x + z @ P['RESIDUAL' + sfx] + bias('RESIDUAL_BIAS' + sfx)
+    h = np.maximum(np.maximum(S, 0) @ P['POST1'] + bias('POST1_BIAS'), 0)
+    return save, h @ P['POST2'] + bias('POST2_BIAS')
 
 
 def oracle_logits(arch, P, got, mel, gc=None, teacher_q=None, clamp_rows=False, monkeypatch=None):

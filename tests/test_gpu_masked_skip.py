@@ -56,9 +56,11 @@ def live_ref(ids):
     return valid, groups(256).astype(np.int32), np.nonzero(groups(32))[0].astype(np.int32)
 
 
-def run(monkeypatch, skip, B, T, q, ids):
+def run(monkeypatch, skip, B, T, q, ids, arch=None, poison_grads=False):
     monkeypatch.setenv('LBWN_SKIP_MASKED', skip)
-    net = make_net(arch3(), B)
+    net = make_net(arch or arch3(), B)
+    if poison_grads:   # "every pointer of the struct is fully overwritten" (include/lbwn.h)
+        net.grad_flat.fill_(float('nan'))
     net.forward(q, None, ids, backward=True)
     torch.cuda.synchronize()
     out = dict(status=int(net.plan_tensor(T, 'status').view(torch.int32)[0]),
@@ -81,16 +83,22 @@ def is_head_weight(name):
 @pytest.mark.parametrize('B,T', SHAPES)
 @pytest.mark.parametrize('pattern', ['all_valid', 'all_zero', 'dealer', 'lone_rows', 'single'])
 def test_masked_skip(monkeypatch, pattern, B, T):
-    arch = arch3()
+    check_masked_skip(monkeypatch, pattern, B, T)
+
+
+def check_masked_skip(monkeypatch, pattern, B, T, arch=None, poison_grads=False):
+    """arch: another arch than arch3 (tests/test_gpu_no_bias.py); poison_grads: NaN in every gradient
+    before each backward."""
+    arch = arch or arch3()
     rng = np.random.default_rng(5)
     q = rng.integers(0, arch['n_quant'], size=(B, T)).astype(np.int32)
     ids = make_ids(pattern, B, T)
     valid, tlive, klive = live_ref(ids)
     M = B * T
 
-    on = run(monkeypatch, '1', B, T, q, ids)
-    on2 = run(monkeypatch, '1', B, T, q, ids)
-    off = run(monkeypatch, '0', B, T, q, ids)
+    on = run(monkeypatch, '1', B, T, q, ids, arch, poison_grads)
+    on2 = run(monkeypatch, '1', B, T, q, ids, arch, poison_grads)
+    off = run(monkeypatch, '0', B, T, q, ids, arch, poison_grads)
     assert on['status'] == 0 and on2['status'] == 0 and off['status'] == 0
     assert any(is_head_weight(n) for n in on['grads'])
 

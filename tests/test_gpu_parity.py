@@ -321,9 +321,11 @@ def test_plan_forward_backward(lib, gemm_mode, which, B, T, mode, chain_tile):
     'small_live_halo' masks 3 positions instead of 37: 37 is more than small_arch's receptive
     field of 30, so in the other small cases no gradient reaches a position t < d and the SAVE
     rows' share of the tap-0 weight gradients is zero (tests/test_gradcheck.py
-    test_mutant_tap0_without_save_rows)."""
+    test_mutant_tap0_without_save_rows).  ('small', 3, 200) starts its backward from gradients filled
+    with NaN: every pointer of the gradient struct is fully overwritten (include/lbwn.h)."""
     gemm_mode(mode)
     check_plan(arch3() if which == 'arch3' else small_arch(), B, T, invalid=3 if which == 'small_live_halo' else 37,
+               poison_grads=(which, B, T) == ('small', 3, 200),
                title='%s B=%d T=%d mode %d %s' % (which, B, T, mode, chain_tile))
 
 
@@ -412,13 +414,30 @@ def check_grads(net, arch, P, cache, dlog, n_valid, s, r2, worst, intermediates=
     return adopted
 
 
-def check_plan(arch, B, T, invalid=37, title=''):
-    net = make_net(arch, B)
+def poison(net):
+    """NaN in every gradient before a backward: "grads: every pointer of the struct is fully
+    overwritten" (include/lbwn.h), so none may survive it."""
+    net.grad_flat.fill_(float('nan'))
+
+
+def all_grads_finite(net):
+    for name, g in net.grads.items():
+        assert bool(torch.isfinite(g).all()), '%s: the backward left part of it unwritten' % name
+
+
+def check_plan(arch, B, T, invalid=37, title='', poison_grads=False, seed=0):
+    """seed: of the parameters (a case whose relu ties pass the cap takes another).  poison_grads: fill net.grad_flat with NaN before the backward and assert that every gradient
+    is finite after it, before the comparisons."""
+    net = make_net(arch, B, seed=seed)
     q, ids = rand_batch(arch, B, T, invalid=invalid)
     P, S, lg, cache, new_save, st, dlog = _run_oracle(arch, net, q, ids)
+    if poison_grads:
+        poison(net)
     net.forward(q, None, ids, backward=True)
     torch.cuda.synchronize()
     assert int(net.plan_tensor(T, 'status').view(torch.int32)[0]) == 0, 'chain hand-off timed out'
+    if poison_grads:
+        all_grads_finite(net)
     L, Cd = R.n_layers(arch), arch['n_dil']
     # forward activations (z before backward overwrote it is not kept: compare SAVE / stats /
     # logits-derived quantities, then per-layer z via a fresh forward below)
@@ -431,7 +450,7 @@ def check_plan(arch, B, T, invalid=37, title=''):
         else:        # deeper layers hold fp32-computed residual activations
             close(net.save_vars[k].cpu().numpy(), v, 1e-5, k)
     # fresh forward with the original SAVE: z of every layer, skip sum, logits
-    net2 = make_net(arch, B)
+    net2 = make_net(arch, B, seed=seed)
     net2.forward(q, None, ids, backward=False)
     torch.cuda.synchronize()
     M = B * T
@@ -446,7 +465,8 @@ def check_plan(arch, B, T, invalid=37, title=''):
         xb = xs[l * stride:l * stride + B * (H + T) * Cr].view(B, H + T, Cr).cpu().double().numpy()
         sfx = '_%d_%d' % (b, bl)
         prev, x = xb[:, H - d:H - d + T], xb[:, H:]
-        v = {nm: prev @ P[nm + sfx][0] + x @ P[nm + sfx][1] + P[nm + '_BIAS' + sfx] for nm in ('SIGNAL', 'GATE')}
+        v = {nm: prev @ P[nm + sfx][0] + x @ P[nm + sfx][1] + (P[nm + '_BIAS' + sfx] if arch['use_bias'] else 0.0)
+             for nm in ('SIGNAL', 'GATE')}
         zl = np.tanh(v['SIGNAL']) * R._sigmoid(v['GATE'])
         np.testing.assert_allclose(z[:, l * Cd:(l + 1) * Cd], zl.reshape(M, Cd), rtol=0, atol=1e-5,
                                    err_msg='z layer %d (identical inputs)' % l)
@@ -454,9 +474,10 @@ def check_plan(arch, B, T, invalid=37, title=''):
     for l in range(L):
         np.testing.assert_allclose(z[:, l * Cd:(l + 1) * Cd], cache['z'][l].reshape(M, Cd), rtol=0, atol=5e-5,
                                    err_msg='z layer %d (end to end)' % l)
-    s = net2.plan_tensor(T, 's').view(M, -1).cpu().numpy()
+    # (the plan pads n_skip / n_post to 4 columns: n_post = 6 of par/arch2.json's widths)
+    s = net2.plan_tensor(T, 's').view(M, -1)[:, :arch['n_skip']].cpu().numpy()
     close(s, cache['S'].reshape(M, -1), 1e-5, 'skip sum')
-    r2 = net2.plan_tensor(T, 'r2').view(M, -1).cpu().numpy()
+    r2 = net2.plan_tensor(T, 'r2').view(M, -1)[:, :arch['n_post']].cpu().numpy()
     close(r2, cache['r2'].reshape(M, -1), 2e-5, 'relu2')
     # gradients: ours are Σxent-grads (raw); the oracle's are of the mean.  The forward is
     # bit-reproducible, so the fresh plan's s / r2 carry the signs the backward above saw.
@@ -518,18 +539,23 @@ def test_plan_conditioning_ragged(chain_tile):
     check_conditioning(1, 1, 32, 3, 136, chain_tile)
 
 
-def check_conditioning(gc, lc, C, B, T, chain_tile, arch=None, seed=0):
+def check_conditioning(gc, lc, C, B, T, chain_tile, arch=None, seed=0, poison_grads=False):
     """arch: another conditioned arch than cond_arch(gc, lc, C) (tests/test_gpu_cond_plan.py); seed:
-    of the parameters.  Returns the net after its backward (its plan_info is then complete)."""
+    of the parameters; poison_grads: as check_plan.  Returns the net after its backward (its plan_info
+    is then complete)."""
     arch = arch or cond_arch(gc, lc, C)
     net = make_net(arch, B, seed=seed)
     q, ids, mel = cond_batch(arch, B, T)
     P, S = oracle_params(net)
     lg, cache, new_save = R.forward(arch, P, q, ids, S, mel=mel)
     st, dlog = R.loss_fcn(arch, P, lg, q, ids, 0.0)
+    if poison_grads:
+        poison(net)
     net.forward(q, mel, ids, backward=True)
     torch.cuda.synchronize()
     assert int(net.plan_tensor(T, 'status').view(torch.int32)[0]) == 0
+    if poison_grads:
+        all_grads_finite(net)
     stats = net.stats.cpu().numpy()
     assert int(stats[1]) == st['n_valid']
     np.testing.assert_allclose(stats[0] / st['n_valid'], st['mean_xent'], rtol=1e-5)
@@ -604,7 +630,11 @@ def test_staged_equals_unstaged_arch3_bitwise(chain_tile):
 
 
 def test_adam_step_matches_oracle():
-    arch = small_arch(nb=1, nbl=3)
+    check_adam_step(small_arch(nb=1, nbl=3))
+
+
+def check_adam_step(arch):
+    """Three steps of the plan + lbwn.optim.AdamOptimizer against the oracle's AdamTF1; returns the net."""
     B, T = 2, 128
     net = make_net(arch, B, l2=1e-3)
     q, ids = rand_batch(arch, B, T)
@@ -627,6 +657,7 @@ def test_adam_step_matches_oracle():
         assert d.max() <= 2 * 3 * 1e-3 + 1e-6, name
         assert np.mean(d) <= 2e-6, (name, np.mean(d))
     assert net.counters[0].item() == 3 and net.counters[1].item() == 3 * st['n_valid']
+    return net
 
 
 @pytest.mark.parametrize('n,nw', [(1003, 501), (4096, 4096), (7, 3), (1, 0)])

@@ -124,7 +124,7 @@ def test_staged_equals_unstaged(gc, lc):
         np.testing.assert_allclose(sv2[k], sv[k], rtol=0, atol=0)
 
 
-@pytest.mark.parametrize('gc,lc,ub', [(0, 0, True), (3, 1, True), (0, 0, False)])
+@pytest.mark.parametrize('gc,lc,ub', [(0, 0, True), (3, 1, True), (0, 0, False), (3, 1, False)])
 def test_backward_finite_difference(gc, lc, ub):
     arch = arch_tiny(gc, lc, ub=ub)
     P, save, q, ids, mel = _setup(arch, T=16)
@@ -157,14 +157,25 @@ def test_backward_finite_difference(gc, lc, ub):
 def test_generation_teacher_forced_equals_training_forward():
     """tests.py:1 intent: imodel and tmodel are equivalent functions.  Teacher-forced
     generation (PRE bias on) with SAVE built from gen's step-0 state == training logits."""
-    arch = arch_tiny(gc=3)
+    _generation_equals_training(True)
+
+
+def test_generation_teacher_forced_equals_training_forward_no_bias():
+    """The same for use_bias = false: no parameter is a bias, and pre_bias has nothing to add."""
+    _generation_equals_training(False)
+
+
+def _generation_equals_training(ub):
+    arch = arch_tiny(gc=3, ub=ub)
     P, _, q, _, _ = _setup(arch, B=1, T=20)
+    assert any('BIAS' in n for n in P) == ub
+    bias = (lambda n: P[n]) if ub else (lambda n: 0.0)
     teacher = q[0]
     gc_id = 2
     _, _, glog = R.generate(arch, P, 1, len(teacher) + 1, teacher_q=teacher, gc_ids=[gc_id],
                             return_logits=True)
     # gen time 0 (zero input) is the step before training position 0: SAVE_l = [0..0, g_l]
-    z0 = np.zeros((1, arch['n_res'])) + P['PRE_BIAS']
+    z0 = np.zeros((1, arch['n_res'])) + bias('PRE_BIAS')
     save = {}
     L = R.n_layers(arch)
     emb = P['GC_EMBED'][[gc_id]]
@@ -175,13 +186,17 @@ def test_generation_teacher_forced_equals_training_forward():
         sv = np.zeros((1, d, arch['n_res']))
         sv[0, -1] = z[0]
         save['SAVE_%d%s' % (d, sfx)] = sv
-        v = {nm: z @ P[nm + sfx][1] + P[nm + '_BIAS' + sfx] + emb @ P['GC_' + nm + sfx]
+        v = {nm: z @ P[nm + sfx][1] + bias(nm + '_BIAS' + sfx) + emb @ P['GC_' + nm + sfx]
              for nm in ('SIGNAL', 'GATE')}
         zz = np.tanh(v['SIGNAL']) * R._sigmoid(v['GATE'])
-        z = z + zz @ P['RESIDUAL' + sfx] + P['RESIDUAL_BIAS' + sfx]
+        z = z + zz @ P['RESIDUAL' + sfx] + bias('RESIDUAL_BIAS' + sfx)
     ids = np.full((1, len(teacher)), gc_id)
     lg, _, _ = R.forward(arch, P, teacher[None, :], ids, save)
     np.testing.assert_allclose(glog[0, 1:], lg[0], rtol=1e-10, atol=1e-10)
+    if not ub:   # no PRE_BIAS for the flag to add
+        _, _, glog0 = R.generate(arch, P, 1, len(teacher) + 1, teacher_q=teacher, gc_ids=[gc_id],
+                                 return_logits=True, pre_bias=False)
+        np.testing.assert_array_equal(glog0, glog)
 
 
 def test_generation_forced_trajectory():

@@ -111,6 +111,34 @@ def test_checkpoint_restores_tf_bundle(tmp_path):
     assert int(dst['GLOBAL_STEP'][0]) == 1234
 
 
+@pytest.mark.parametrize('use_bias', [True, False])
+def test_tf_bundle_import_loads_exactly_the_layout(tmp_path, use_bias):
+    """A TF V2 bundle holding a reference net's variables (serial names, int32 scalar counters;
+    use_bias = false: no *_BIAS variable) restores into WaveNetTrain: the bundle's names are exactly
+    the net's saveable names -- none missing, none extra -- and every tensor arrives bit for bit."""
+    from lbwn.arch import normalize_arch
+    from lbwn.tmodel import WaveNetTrain
+    arch = normalize_arch(dict(n_blocks=1, n_block_layers=3, n_quant=256, n_res=8, n_dil=8, n_skip=16, n_post=8,
+                               n_gc_embed=4, n_gc_category=3, n_lc_in=5, n_lc_out=6, lc_upsample=[2, 2],
+                               use_bias=use_bias))
+    net = WaveNetTrain(**arch, batch_sz=2, l2_factor=0.0, device='cpu', ckpt_path=str(tmp_path / 'run.net'),
+                       resume_step=1000)
+    rng = np.random.default_rng(1)
+    t = {n: rng.standard_normal(tuple(v.shape)).astype(np.float32) for n, v in net.vars.items()}
+    t.update({n: rng.standard_normal(tuple(v.shape)).astype(np.float32) for n, v in net.save_vars.items()})
+    t['GLOBAL_STEP'] = np.array(1000, dtype=np.int32)
+    t['VALID_SAMPLES'] = np.array(4242, dtype=np.int32)
+    assert any('BIAS' in n for n in t) == use_bias
+    tfckpt.write_bundle(str(tmp_path / 'run.net-1000'), t)
+    loaded = net.restore()
+    assert set(loaded) == set(t) == set(net.state_tensors())
+    for n, v in net.vars.items():
+        np.testing.assert_array_equal(v.numpy(), t[n], err_msg=n)
+    for n, v in net.save_vars.items():
+        np.testing.assert_array_equal(v.numpy(), t[n], err_msg=n)
+    assert int(net.counters[0]) == 1000 and int(net.counters[1]) == 4242 and net.global_step_host == 1000
+
+
 def test_export_and_cli_roundtrip(tmp_path):
     st = {'PRE_0': torch.randn(256, 32), 'GLOBAL_STEP': torch.tensor([77], dtype=torch.int64),
           'VALID_SAMPLES': torch.tensor([5], dtype=torch.int64)}
