@@ -350,7 +350,7 @@ int lbwn_split_planes(const float* W, int64_t ldw, int rows, int K, int trans, u
  *             ([splits][M][N]) and the split count actually used is stored here (1: C was written);
  *             plain products only.
  * Combinations the chosen kernel would not honour are refused with EINVAL before any launch.
- * (Not exposed: the one-hot A operand lbwn_gemm_args::a_codes and the lean launcher.) */
+ * (Not exposed: the one-hot A operand lbwn_gemm_args::a_codes.) */
 typedef struct lbwn_gemm_ex_args {
   size_t struct_size;
   const float* A; const float* B; float* C;

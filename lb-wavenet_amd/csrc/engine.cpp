@@ -206,7 +206,7 @@ size_t carve(size_t& cur, size_t bytes) {
   return o;
 }
 
-// rows of the SG buffer: whole 32-row blocks (sg_off in layer.hip)
+// rows of the SG buffer: whole 32-row blocks (sg_off in layer_common.h)
 static long m32(long M) { return (M + 31) / 32 * 32; }
 
 // Split-K for the weight-gradient GEMMs (K = B·T positions).  One 4-wave block per CU
@@ -365,7 +365,7 @@ int lbwn_plan_create(const lbwn_arch* a, int B, int T, lbwn_plan** out) {
   p->Ge = a->n_gc_embed;
   p->ncat1 = a->n_gc_embed > 0 ? a->n_gc_category + 1 : 0;
   p->Lo = a->n_lc_out;
-  {  // XCD-grouped chain tile walk (layer.hip chain_first): on for LC archs only.  Same box, two
+  {  // XCD-grouped chain tile walk (layer_common.h chain_first): on for LC archs only.  Same box, two
      // rounds (profiles/r04_ab_chain_xcd_lc.txt): arch5 B=8 2.748-2.761 vs 2.777-2.779 ms (the
      // LC products read the k-blocked DV export the chain wrote), arch3 B=8 2.101-2.104 vs
      // 2.082-2.091 (its forward chain 248 vs 239-240 us; profiles/r04_ab_handoff_xcd.txt).

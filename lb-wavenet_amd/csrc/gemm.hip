@@ -26,8 +26,7 @@ constexpr int NT = 256;
 // and 4·(BMN+8) ≡ 32 (mod 64 banks) puts the halves on disjoint banks
 constexpr int MNPAD = 8;
 
-// BK = 16: the default (37 KB LDS, 2 blocks/CU).  BK = 8: the lean variant (21 KB) that fits
-// beside a resident persistent chain block (131 KB) to run weight-gradient GEMMs concurrently.
+// BK = 16 (37 KB LDS, 2 blocks/CU) is the one depth instantiated.
 template <bool KC, int BMN, int BK>
 struct Stage {
   static constexpr int SREG = BK * BMN / (4 * NT);   // float4 staging registers per thread
@@ -1430,17 +1429,6 @@ int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int 
   LBWN_REQUIRE(a.colpart == nullptr && a.step_advance == nullptr && !a.c_chain_ls,
                "gemm: column partials / the step counter / chain-order C need the bf16-split form");
   return gemm_launch_t<16, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
-}
-
-int lbwn_gemm_launch_lean(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
-                          hipStream_t st) {
-  g_last_form = "";
-  if (lbwn_gemm_mode() == 1 && a.a_codes == nullptr && a.K >= 4 && a.M >= 4 && a.N >= 4)
-    return gemm_launch_x3(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
-  LBWN_REQUIRE(!a.row_live && !a.k_live && !a.nk_live && !a.k_pre, "gemm: row_live / k_live need the bf16-split form");
-  LBWN_REQUIRE(!a.mbits && !a.mbits_out, "gemm: mask bits need the bf16-split form");
-  LBWN_REQUIRE(a.colpart == nullptr, "gemm: column partials need the bf16-split form");
-  return gemm_launch_t<8, 128, 128>(a, a_kcontig, b_kcontig, split_k, slab_ws, st);
 }
 
 size_t lbwn_split_planes_elems(int rows, int K) { return (size_t)rows * ((K + X3_BK - 1) / X3_BK) * 3 * X3_BK; }

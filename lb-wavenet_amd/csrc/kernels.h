@@ -21,7 +21,7 @@ struct lbwn_gemm_args {
   long long* step_advance;   // nullable, bf16-split form only: block 0 adds 1 (the per-step generator's counter)
   // bf16-split form, no split-K / accumulate / mask: > 0 stores C in the backward chain's row-load
   // order instead of rows (ldc unused): 32-column block j at C + j·c_chain_ls, element (m, c) at
-  // sg_off(m, c / 8, (c / 4) & 1) + c % 4 (layer.hip), so the chain's own-row loads are 1-KiB runs.
+  // sg_off(m, c / 8, (c / 4) & 1) + c % 4 (layer_common.h), so the chain's own-row loads are 1-KiB runs.
   // The A-in-registers forms (gemm_x3q_kernel) store the raw sums in this order: there the launcher
   // also refuses bias / relu_out / mbits / mbits_out; the LDS-staged forms apply bias and relu_out
   long c_chain_ls;
@@ -71,7 +71,7 @@ bool lbwn_gemm_x3q8_form(int M, int N, int K, int a_kcontig, int presplit, int r
 inline long lbwn_gemm_mbits_words(long M, long N) { return ((M + 255) / 256) * ((N + 127) / 128) * 8 * 64; }
 int lbwn_gemm_launch(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
                      hipStream_t st);
-// the kernel instantiation the most recent lbwn_gemm_launch / _lean on this thread chose (the names
+// the kernel instantiation the most recent lbwn_gemm_launch on this thread chose (the names
 // of include/lbwn.h lbwn_gemm_last_form; "" while the call has launched nothing)
 const char* lbwn_gemm_last_form_impl(void);
 inline int lbwn_colpart_parts(long M) { return (int)((M + 255) / 256); }
@@ -84,9 +84,6 @@ int lbwn_split_planes_launch(int njobs, const float* const* W, const long* ldw, 
 // 1: bf16-split (default), 0: f32 MFMA (gemm.hip)
 int lbwn_gemm_mode(void);
 int lbwn_gemm_set_mode_impl(int mode);
-// same product with a 21 KB LDS footprint (BK = 8) so it can co-reside with a chain block
-int lbwn_gemm_launch_lean(const lbwn_gemm_args& a, int a_kcontig, int b_kcontig, int split_k, float* slab_ws,
-                          hipStream_t st);
 
 // One residual layer (tmodel.py:117-184).  x buffers are [B][H+T][Cr]; rows [H-d, H) of
 // x_in hold the D-separation state SAVE_l (prepended by lbwn_dsep_prepend).
@@ -125,10 +122,7 @@ int lbwn_layer_bwd_launch(const lbwn_layer_args& a, hipStream_t st);
 int lbwn_layer_slab_stride();
 // split weight images for the forward chain's bf16-split products (bf16 elements per layer)
 int lbwn_layer_image_x3_elems();
-// lbwn_pack_layers_x3_launch + lbwn_pack_layers_bx3_launch in one launch, plus (skip_b, bsum
-// non-null) bsum[n] = Σ_l skip_b[l·Cs + n] (lbwn_sum_bias_launch)
-// ... and (lcout non-null) the L split LC images of the in-chain LC term (lbwn_lc_image_x3_elems each)
-// The training step's start-of-step work in one launch (layer.hip step_prologue_kernel): the
+// The training step's start-of-step work in one launch (pack.hip step_prologue_kernel): the
 // arguments of lbwn_pack_layers_fb_x3_launch, lbwn_split_planes_launch (njobs 0..6),
 // lbwn_embed_launch, lbwn_dsep_prepend_launch and lbwn_zero_launch (zero_bytes may be 0).
 struct lbwn_prologue_args {
@@ -161,6 +155,10 @@ struct lbwn_prologue_args {
   int *tlive, *klive, *nklive, *kpre;
 };
 int lbwn_step_prologue_launch(const lbwn_prologue_args& a, hipStream_t st);
+// Both chains' split images in one launch: the L forward images (fout, lbwn_layer_image_x3_elems
+// each) and the L backward images (bout, lbwn_layer_image_bx3_floats each), plus (skip_b, bsum
+// non-null) bsum[n] = Σ_l skip_b[l·Cs + n] (lbwn_sum_bias_launch)
+// ... and (lcout non-null) the L split LC images of the in-chain LC term (lbwn_lc_image_x3_elems each)
 int lbwn_pack_layers_fb_x3_launch(const float* sig, const float* gate, const float* sig_b, const float* gate_b,
                                   const float* res, const float* res_b, unsigned short* fout, float* bout, int L,
                                   int Cr, int Cd, const float* skip_b, int Cs, float* bsum, const float* lc_sig,
@@ -172,16 +170,11 @@ int lbwn_lc_image16_elems();       // the 16-lane forward chain's LC image (lc16
 // 16-position waves (chain_fwd16_kernel) with 4 / 8 waves = 64- / 128-position tiles
 int lbwn_chain_fwd_tile(int fwd_nw);
 int lbwn_lc_in_chain_ok(int Lo);   // n_lc_out the forward chain's in-chain LC term supports
-int lbwn_pack_layers_x3_launch(const float* sig, const float* gate, const float* sig_b, const float* gate_b,
-                               const float* res, const float* res_b, unsigned short* out, int L, int Cr, int Cd,
-                               hipStream_t st);
 int lbwn_layer_image_floats();
 int lbwn_layer_dx_combine_launch(const float* out_a, const float* out_c0, float* dx, int B, int T, int H, int d, int C,
                                  hipStream_t st);
 // backward split images (WD bf16 + Rs f32) for the bf16-split backward chain, floats per layer
 int lbwn_layer_image_bx3_floats();
-int lbwn_pack_layers_bx3_launch(const float* sig, const float* gate, const float* res, float* out, int L, int Cr,
-                                int Cd, hipStream_t st);
 int lbwn_layer_nblocks(int B, int T);
 int lbwn_layer_bwd_grid(int B, int T);   // = number of slab partials per layer
 int lbwn_pack_layers_launch(const float* sig, const float* gate, const float* sig_b, const float* gate_b,
@@ -211,7 +204,7 @@ struct lbwn_chain_args {
   long long* trace = nullptr;  // debug: cycle stamps of block trace_blk, [L][16] (LBWN_CHAIN_TRACE)
   int trace_blk = 0;
   // bf16-split backward (chain_bwd_x3_kernel): σ(v_gate) rows [L][M][32] written by the X3
-  // forward chain (layer stride sgls floats), and the backward images (lbwn_pack_layers_bx3)
+  // forward chain (layer stride sgls floats), and the backward images (lbwn_pack_layers_fb_x3)
   float* SG = nullptr; long sgls = 0;
   const float* bimg = nullptr;
   int* tile_gid = nullptr;     // x3 backward + GC: [ntiles] uniform voice id per tile or -1
@@ -219,13 +212,12 @@ struct lbwn_chain_args {
   const float* lcact = nullptr; const unsigned short* lcimg = nullptr; int Lo = 0;
   int fwd_nw = 0;              // forward form (lbwn_chain_fwd_tile); lcimg in the matching layout
   int bwd_nw = 0;              // backward form: 0 = chain_bwd_x3_kernel (128), 4 / 8 = chain_bwd16_kernel
-  int xcd = 0;                 // XCD-grouped tile walk (layer.hip chain_first)
+  int xcd = 0;                 // XCD-grouped tile walk (layer_common.h chain_first)
   long dvks = 0;               // x3 backward forms: dv_out k-blocked ([L·2][Mp][32], chunk stride dvks)
 };
 int lbwn_chain_fwd_launch(const lbwn_chain_args& c, hipStream_t st);
 int lbwn_chain_bwd_launch(const lbwn_chain_args& c, hipStream_t st);
 int lbwn_layer_reduce_all_launch(const lbwn_layer_red_args& r, int L, long slab_layer, hipStream_t st);
-int lbwn_chain_fwd_lds_bytes();
 
 // D-separation state transfer for ALL layers at once.
 int lbwn_dsep_prepend_launch(float* xall, long xlayer_stride, const float* save, int L, int nbl,
@@ -235,8 +227,6 @@ int lbwn_dsep_save_launch(const float* xall, long xlayer_stride, float* save, in
 
 int lbwn_embed_launch(const int* q, const float* pre, const float* pre_b, float* x0, int B, int T, int H,
                       int Cr, int Q, hipStream_t st);
-int lbwn_embed_bwd_launch(const int* q, const float* ga, const float* gc0, int gd, float* dpre,
-                          float* dpre_b, float* ws, int B, int T, int Cr, int Q, hipStream_t st);
 
 struct lbwn_head_args {
   float* logits;            // [M][Q] in: logits, out: dlogits (unnormalised: (softmax-onehot)·mask)
@@ -254,8 +244,6 @@ int lbwn_stats_reduce_launch(const float* partial, int nparts, float* stats, hip
 // several column sums in one launch pair; ws holds Σ_j lbwn_colsum_ws_floats(M, N[j]) floats
 int lbwn_colsum_multi_launch(int njobs, const float* const* X, const long* ldx, const int* N, float* const* out,
                              const int* accumulate, int M, float* ws, hipStream_t st);
-int lbwn_colsum_launch(const float* X, long ldx, int M, int N, float* out, int accumulate, float* ws,
-                       hipStream_t st);
 int lbwn_colsum_ws_floats(int M, int N);
 // the two passes apart: the first pass alone (*nparts = its partial row count; ws holds that ×
 // N floats), and the second over any partials (first-pass ones or a GEMM epilogue's colpart)
@@ -264,7 +252,6 @@ int lbwn_colsum_final_launch(int njobs, float* const* parts, const int* N, float
                              const int* nparts, hipStream_t st,
                              const int* reps = nullptr);
 int lbwn_sum_bias_launch(const float* b, int L, int N, float* out, hipStream_t st);
-int lbwn_fill_launch(float* p, float v, long n, hipStream_t st);
 
 int lbwn_adam_launch2(float* params, const float* grads, float* m, float* v, long n_weights, long n_total,
                       float lr, float b1, float b2, float eps, float l2, const float* stats,
@@ -276,8 +263,6 @@ int lbwn_counters_launch(long long* counters, const float* stats, int adam_appli
 int lbwn_pre_grad_ws_floats(int Q, int Cr);
 int lbwn_pre_grad_launch(const int* q, const float* g, const float* dprev, int gd, int B, int T, int Cr, int Q,
                          float* dpre, float* dpre_b, float* ws, hipStream_t st);
-int lbwn_shift_add_launch(float* out, const float* a, const float* c0, int gd, int B, int T, int C,
-                          hipStream_t st);
 
 int lbwn_mulaw_encode_launch(const float* x, int* q, long n, int n_quanta, int tf32, hipStream_t st);
 int lbwn_mulaw_decode_launch(const int* q, float* x, long n, int n_quanta, hipStream_t st);

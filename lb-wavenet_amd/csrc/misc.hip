@@ -27,24 +27,12 @@ __global__ void embed_kernel(const int* __restrict__ q, const float* __restrict_
   embed_flat_body(blockIdx.x, gridDim.x, q, pre, pre_b, x0, B, T, H, Cr, Q, v4);
 }
 
-// out[m] = a[m] + (t+gd < T ? c0[m+gd] : 0)   (dx of a layer input from (g + dcur, dprev))
-__global__ void shift_add_kernel(float* out, const float* a, const float* c0, int gd, int B, int T, int C) {
-  const long n = (long)B * T * C;
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    const long m = e / C;
-    const int t = (int)(m % T);
-    float v = a[e];
-    if (t + gd < T) v += c0[e + (long)gd * C];
-    out[e] = v;
-  }
-}
-
 // ---- PRE-embedding gradient -------------------------------------------------------------
 // dPRE[q][c] = Σ_{t: code_t = q} dx0[t][c] and dPRE_B[c] = Σ_t dx0[t][c]: the transpose of the
 // one-hot product (tmodel.py:64-66; tf.one_hot: a code outside [0, Q) has no row).  A scatter
 // into an LDS histogram, not a dense GEMM against the one-hot matrix (K = B·T, M = Q, N = Cr:
 // ~200 µs of tiles that are almost all zeros).  dx0 = g + shift(dprev) (layer 0's input
-// gradient, as shift_add forms it) is formed on the fly and never stored.  Each wave of a block
+// gradient) is formed on the fly and never stored.  Each wave of a block
 // owns an LDS histogram and a contiguous sub-chunk of the block's positions, walked two positions
 // per instruction (half-wave h takes h, h+2, ...) with no-return LDS float atomics (ds_add_f32:
 // no read-modify-write round trip); a single wave's atomics are applied in program and lane
@@ -456,10 +444,6 @@ __global__ void sum_bias_kernel(const float* b, int L, int N, float* out) {
   out[n] = s;
 }
 
-__global__ void fill_kernel(float* p, float v, long n) {
-  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) p[e] = v;
-}
-
 // ---- TF1 Adam over the flat parameter buffer --------------------------------------------------
 // grads hold Σ-xent gradients; g = raw·(1/n_valid) + l2·θ for the weight region
 // [0, n_weights) (non-BIAS vars, tmodel.py:250-261); biases get no l2 term.
@@ -621,13 +605,6 @@ int lbwn_pre_grad_launch(const int* q, const float* g, const float* dprev, int g
   return 0;
 }
 
-int lbwn_shift_add_launch(float* out, const float* a, const float* c0, int gd, int B, int T, int C,
-                          hipStream_t st) {
-  shift_add_kernel<<<grid_for((long)B * T * C), 256, 0, st>>>(out, a, c0, gd, B, T, C);
-  LBWN_CHECK_LAUNCH();
-  return 0;
-}
-
 int lbwn_head_launch(const lbwn_head_args& a, int* nblocks_out, hipStream_t st) {
   const long M = (long)a.B * a.T;
   LBWN_REQUIRE(!a.colpart || a.Q <= 512, "head: column partials need Q <= 512");
@@ -704,19 +681,8 @@ int lbwn_colsum_final_launch(int njobs, float* const* parts, const int* N, float
   return 0;
 }
 
-int lbwn_colsum_launch(const float* X, long ldx, int M, int N, float* out, int accumulate, float* ws,
-                       hipStream_t st) {
-  return lbwn_colsum_multi_launch(1, &X, &ldx, &N, &out, &accumulate, M, ws, st);
-}
-
 int lbwn_sum_bias_launch(const float* b, int L, int N, float* out, hipStream_t st) {
   sum_bias_kernel<<<(N + 63) / 64, 64, 0, st>>>(b, L, N, out);
-  LBWN_CHECK_LAUNCH();
-  return 0;
-}
-
-int lbwn_fill_launch(float* p, float v, long n, hipStream_t st) {
-  fill_kernel<<<grid_for(n), 256, 0, st>>>(p, v, n);
   LBWN_CHECK_LAUNCH();
   return 0;
 }

@@ -1,5 +1,5 @@
 // Device bodies of the training step's independent start-of-step work, shared by their
-// stand-alone kernels (misc.hip, gemm.hip) and by the fused step-prologue launch (layer.hip,
+// stand-alone kernels (misc.hip, gemm.hip) and by the fused step-prologue launch (pack.hip,
 // lbwn_step_prologue_launch): each body walks its own index space over a range of `nblk` blocks
 // of 256 threads, `blk` being this block's index within that range.
 #pragma once

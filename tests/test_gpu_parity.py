@@ -723,7 +723,7 @@ def test_chain_xcd_walk_lc_bitwise(monkeypatch):
 @pytest.mark.parametrize('env', [{'LBWN_CHAIN_XCD': '1'}, {'LBWN_DZ_XCD': '0'}])
 def test_placement_switches_bitwise(monkeypatch, env):
     """The placement-only switches change which block (and so which XCD) computes a tile, never
-    the arithmetic of a tile: the XCD-grouped chain walk (layer.hip chain_first) and dZ's 1-D
+    the arithmetic of a tile: the XCD-grouped chain walk (layer_common.h chain_first) and dZ's 1-D
     tile remap instead of the 2-D XCD blocking (gemm.hip xcd2d_tile) give the default plan's
     outputs and gradients bit for bit (arch3, 128 tiles per chain)."""
     arch = arch3()
