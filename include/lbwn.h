@@ -223,6 +223,37 @@ int lbwn_gen_is_persistent(const lbwn_gen_plan* plan);
  * are clamped into it. */
 int lbwn_gen_prefill(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* codes,
                      int64_t ld_codes, int64_t n, void* stream);
+/* Teacher-forced scoring: log p(code | history) of a known waveform under the model, per step and per
+ * stream (added after ABI 5 was declared, same ABI: two symbols added, none altered).
+ * codes, ld_codes and n are lbwn_gen_prefill's.  With t0 the device step counter at the call, step t0+j
+ * takes the input lbwn_gen_prefill gives it (the pending input for j = 0, codes[b][j-1] after that), and
+ * its logits l_j are those lbwn_gen_run would compute at that step (the same GC term, LC row r(t0+j) and
+ * pre_bias).  logp[b*ld_logp + j] = l_j[c] - logsumexp(l_j), c = codes[b][j] clamped into [0, n_quant):
+ * the natural log of the probability of the code the prompt holds at that step.  The sampling settings
+ * (lbwn_gen_set_sampling) do not enter it.  All n positions of all batch_sz streams are written; logp is
+ * device fp32, ld_logp >= n, columns past n are not touched.
+ * State: the call changes the state exactly as lbwn_gen_prefill(codes, ld_codes, n) does -- rings,
+ * pending code, step counter and the persistent groups' counters are bitwise those of a prefill of the
+ * same codes on the same plan, "samples" / "wav" hold the prompt over the scored steps -- and in addition
+ * leaves "logits" = l_{n-1} for every stream.  To score without advancing, wrap the call in
+ * lbwn_gen_state_save / lbwn_gen_state_load.
+ * Per slice of T_s positions (lbwn_gen_prefill's slices, LBWN_GEN_PREFILL_SLICE included) the layers write
+ * their gate outputs side by side into Zcat [B·T][L·n_dil]; the head is lbwn_gen_run's three GEMMs over
+ * those rows (skip as one product with K = L·n_dil, post1, post2), then one wave per row forms the
+ * log-softmax gather.
+ * scratch: caller-owned device memory, 16-byte aligned, lbwn_gen_score_scratch_bytes(plan) bytes (0 for a
+ * NULL plan): Zcat [R][L·n_dil] | S [R][n_skip] | H [R][n_post] | LG [R][n_quant] fp32 with R =
+ * batch_sz·T_s rows, each part rounded up to 256 bytes.  It does not depend on n or max_steps; the plan's
+ * workspace is what it was without this call.
+ * Stream-ordered, no host synchronisation or allocation, graph-capturable (t0 is read on the device); at
+ * t0 = 0 or in the middle of a run, any number of times.
+ * EINVAL before any launch, naming the argument: every refusal of lbwn_gen_prefill; logp or scratch NULL;
+ * scratch not 16-byte aligned; ld_logp < n; n_skip, n_post, n_quant or L·n_dil not a multiple of 4, SKIP /
+ * POST1 / POST2 NULL or not 16-byte aligned (what the GEMMs take); batch_sz*T_s*max(L·n_dil, n_skip,
+ * n_post, n_quant) >= 2^31. */
+size_t lbwn_gen_score_scratch_bytes(const lbwn_gen_plan* plan);
+int lbwn_gen_score(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const int* codes,
+                   int64_t ld_codes, int64_t n, float* logp, int64_t ld_logp, void* scratch, void* stream);
 /* Temperature, top-k and nucleus (top-p) filtering of the draw (added after ABI 5 was declared, same
  * ABI: two symbols added, none altered -- the convention of the LC widening of lbwn_gen_prefill).
  * With l a stream's logits at a step (the values "logits" holds, which stays raw):

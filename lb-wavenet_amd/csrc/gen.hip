@@ -28,6 +28,9 @@
 // of the namespace below, the step kernels know nothing of it.  LC plans project the slice's lc
 // rows for G layers at a time on the f32 matrix cores (gen_prefill_lcproj_kernel) into the
 // per-row cond term that kernel already takes.
+// Teacher-forced scoring (lbwn_gen_score): the same host loop with every layer's z kept side by side
+// in a caller-owned Zcat, the per-step GEMM form's head over all rows of a slice, and one wave per
+// row for logp = logit[code] - logsumexp (gen_score_logp_kernel).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1555,6 +1558,51 @@ __global__ void gen_prefill_finish_kernel(const int* codes, long ld_codes, long 
   if (threadIdx.x == 0) *step = t1;
 }
 
+// ---- teacher-forced scoring (lbwn_gen_score) -----------------------------------
+// The head over every position of a prefill slice leaves its logits LG [B·T][Q] (row b·T + j = step
+// t0 + off + j of stream b).  One wave per row: logp[b][off + j] = LG[c] - (m + log Σ exp(LG - m)) with
+// c = the prompt's code at that step and m the row's max.  Each lane holds up to two float4 (Q <= 512,
+// Q % 4 == 0); lanes past Q / 4 idle with -inf / 0.  last (nullable, the call's last slice): row T - 1
+// of every stream is also the plan's "logits".
+struct ScoreK {
+  const float* lg; const int* codes; float* logp; float* last;
+  long ld_codes, ld_logp, off;
+  int B, T, Q;
+};
+constexpr int SC_ROWS = 4;   // rows (waves) per block
+__global__ __launch_bounds__(64 * SC_ROWS) void gen_score_logp_kernel(ScoreK a) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * SC_ROWS + (threadIdx.x >> 6);
+  if (r >= (long)a.B * a.T) return;   // whole waves leave: the DPP steps below see 64 lanes
+  const int b = (int)(r / a.T), j = (int)(r % a.T);
+  const float* row = a.lg + r * a.Q;
+  const int nq = a.Q >> 2;
+  floatx4 v[2];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if (lane + 64 * i < nq) {
+      v[i] = *(const floatx4*)(row + 4 * (lane + 64 * i));
+      mx = fmaxf(fmaxf(mx, fmaxf(v[i][0], v[i][1])), fmaxf(v[i][2], v[i][3]));
+    }
+  }
+  mx = wave_max(mx);
+  float se = 0.f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    if (lane + 64 * i < nq) se += (expf(v[i][0] - mx) + expf(v[i][1] - mx)) + (expf(v[i][2] - mx) + expf(v[i][3] - mx));
+  se = wave_sum(se);
+  if (lane == 0) {
+    const int c = prefill_clamp(a.codes[(long)b * a.ld_codes + a.off + j], a.Q);
+    a.logp[(long)b * a.ld_logp + a.off + j] = row[c] - (mx + logf(se));
+  }
+  if (a.last && j == a.T - 1) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (lane + 64 * i < nq) *(floatx4*)(a.last + (long)b * a.Q + 4 * (lane + 64 * i)) = v[i];
+  }
+}
+
 // ---- state snapshot (lbwn_gen_state_save / lbwn_gen_state_load) ----------------
 // What a run is between two launches: the rings, the pending codes, the step counter (and the
 // persistent groups' copies of it).  The snapshot is stream-major -- a 256-byte header, then per
@@ -2155,18 +2203,32 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
 }
 
 // ---- parallel prompt prefill ----------------------------------------------------------------
-extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const int* codes, int64_t ld_codes,
-                                int64_t n, void* stream) {
-  LBWN_REQUIRE(p && P && ws && codes, "prefill: null argument");
-  LBWN_REQUIRE(n >= 1, "prefill: n must be >= 1 (got %lld)", (long long)n);
-  LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "prefill: ld_codes %lld must be 0 (one shared vector) or >= n = %lld",
+// the refusals lbwn_gen_prefill and lbwn_gen_score share (what: the call's name in the message)
+static int prefill_check(const char* what, const lbwn_gen_plan* p, const lbwn_params* P, const void* ws,
+                         const int* codes, int64_t ld_codes, int64_t n) {
+  LBWN_REQUIRE(p && P && ws && codes, "%s: null argument", what);
+  LBWN_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
+  LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "%s: ld_codes %lld must be 0 (one shared vector) or >= n = %lld", what,
                (long long)ld_codes, (long long)n);
   LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded,
-               "prefill: local conditioning is not supported before lbwn_gen_set_mel (no mel loaded)");
-  LBWN_REQUIRE(p->Lo == 0 || (P->lc_sig && P->lc_gate), "prefill: LC_SIGNAL/LC_GATE pointers are null");
-  LBWN_REQUIRE((long long)p->B * p->pfT * p->Cr < (1LL << 31), "prefill: batch_sz %d x slice %d x n_res %d >= 2^31",
+               "%s: local conditioning is not supported before lbwn_gen_set_mel (no mel loaded)", what);
+  LBWN_REQUIRE(p->Lo == 0 || (P->lc_sig && P->lc_gate), "%s: LC_SIGNAL/LC_GATE pointers are null", what);
+  LBWN_REQUIRE((long long)p->B * p->pfT * p->Cr < (1LL << 31), "%s: batch_sz %d x slice %d x n_res %d >= 2^31", what,
                p->B, p->pfT, p->Cr);
-  hipStream_t st = (hipStream_t)stream;
+  return 0;
+}
+
+// lbwn_gen_score's part of a prefill: the caller's logp and the scratch [Zcat | S | H | LG]
+struct ScoreRun {
+  float* logp; long ld_logp;
+  float *zcat, *S, *H, *LG;
+};
+
+// sc == nullptr: the prefill, launch for launch.  Otherwise every layer's z goes to its column block of
+// Zcat [B·T][L·Cd] instead of the per-layer scratch, and each slice ends with the head over its rows
+// (skip as ONE GEMM with K = L·Cd, post1, post2: gen_run_gemm's three products) and gen_score_logp_kernel.
+static int gen_prefill_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const int* codes, int64_t ld_codes,
+                           int64_t n, const ScoreRun* sc, hipStream_t st) {
   const int B = p->B, L = p->L, H = p->pfH, Cr = p->Cr, Cd = p->Cd;
   float* X[2] = {gat<float>(ws, p->oPFX[0]), gat<float>(ws, p->oPFX[1])};
   float* Z = gat<float>(ws, p->oPFZ);
@@ -2235,11 +2297,35 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
       lbwn_layer_args a;
       memset(&a, 0, sizeof(a));
       a.x_in = X[l & 1]; a.x_out = l + 1 < L ? X[(l + 1) & 1] : nullptr;   // the last layer's output is not needed
-      a.z = Z; a.ldz = Cd; a.wpack = img + (long)l * WI;
+      if (sc) { a.z = sc->zcat + (long)l * Cd; a.ldz = (long)L * Cd; }
+      else { a.z = Z; a.ldz = Cd; }
+      a.wpack = img + (long)l * WI;
       if (gc) { a.gc_tab = gtab + (long)l * B * 2 * Cd; a.gc_ld = 2L * Cd; a.ids = ids; }
       if (p->Lo > 0) { a.cond = pfcond + (long)(l % p->pfG) * 2 * Cd; a.ldcond = ldcond; }   // GC and LC add, as in training
       a.B = B; a.T = T; a.H = H; a.d = x.dw; a.Cr = Cr; a.Cd = Cd;
       if (int e2 = lbwn_layer_fwd_launch(a, st)) return e2;
+    }
+    if (sc) {
+      lbwn_gemm_args sk, p1, p2;
+      memset(&sk, 0, sizeof(sk));
+      sk.A = sc->zcat; sk.lda = (long)L * Cd; sk.B = P->skip; sk.ldb = p->Cs; sk.C = sc->S; sk.ldc = p->Cs;
+      sk.M = B * T; sk.N = p->Cs; sk.K = L * Cd; sk.bias = P->skip_b ? gat<float>(ws, p->oBSUM) : nullptr;
+      p1 = sk;
+      p1.A = sc->S; p1.lda = p->Cs; p1.relu_a = 1; p1.B = P->post1; p1.ldb = p->Cp; p1.C = sc->H; p1.ldc = p->Cp;
+      p1.N = p->Cp; p1.K = p->Cs; p1.bias = P->post1_b; p1.relu_out = 1;
+      p2 = p1;
+      p2.A = sc->H; p2.lda = p->Cp; p2.relu_a = 0; p2.B = P->post2; p2.ldb = p->Q; p2.C = sc->LG; p2.ldc = p->Q;
+      p2.N = p->Q; p2.K = p->Cp; p2.bias = P->post2_b; p2.relu_out = 0;
+      if (int e2 = lbwn_gemm_launch(sk, 1, 0, 1, nullptr, st)) return e2;
+      if (int e2 = lbwn_gemm_launch(p1, 1, 0, 1, nullptr, st)) return e2;
+      if (int e2 = lbwn_gemm_launch(p2, 1, 0, 1, nullptr, st)) return e2;
+      ScoreK k;
+      k.lg = sc->LG; k.codes = codes; k.logp = sc->logp;
+      k.last = off + T == n ? gat<float>(ws, p->oLOG) : nullptr;
+      k.ld_codes = (long)ld_codes; k.ld_logp = sc->ld_logp; k.off = (long)off;
+      k.B = B; k.T = T; k.Q = p->Q;
+      gen_score_logp_kernel<<<(unsigned)(((long)B * T + SC_ROWS - 1) / SC_ROWS), 64 * SC_ROWS, 0, st>>>(k);
+      LBWN_CHECK_LAUNCH();
     }
   }
   gen_prefill_out_kernel<<<grid((long)B * n), 256, 0, st>>>(codes, (long)ld_codes, (long)n, step, gat<int>(ws, p->oSAMP),
@@ -2251,6 +2337,57 @@ extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws
                                                reinterpret_cast<long long*>(g + p->n_gran_core), p->pgroups, B, p->Q);
   LBWN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int lbwn_gen_prefill(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const int* codes, int64_t ld_codes,
+                                int64_t n, void* stream) {
+  if (int e = prefill_check("prefill", p, P, ws, codes, ld_codes, n)) return e;
+  return gen_prefill_run(p, P, ws, codes, ld_codes, n, nullptr, (hipStream_t)stream);
+}
+
+// ---- teacher-forced scoring -------------------------------------------------------------------
+// the scratch of lbwn_gen_score: Zcat [R][L·Cd] | S [R][Cs] | H [R][Cp] | LG [R][Q], R = B·T_s rows, each
+// part rounded up to 256 bytes
+static void score_carve(const lbwn_gen_plan* p, size_t (&off)[4], size_t& total) {
+  const size_t rows = (size_t)p->B * p->pfT;
+  const size_t cols[4] = {(size_t)p->L * p->Cd, (size_t)p->Cs, (size_t)p->Cp, (size_t)p->Q};
+  size_t cur = 0;
+  for (int i = 0; i < 4; ++i) off[i] = gcarve(cur, 4 * rows * cols[i]);
+  total = cur;
+}
+
+extern "C" size_t lbwn_gen_score_scratch_bytes(const lbwn_gen_plan* p) {
+  if (!p) return 0;
+  size_t off[4], total;
+  score_carve(p, off, total);
+  return total;
+}
+
+extern "C" int lbwn_gen_score(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const int* codes, int64_t ld_codes,
+                              int64_t n, float* logp, int64_t ld_logp, void* scratch, void* stream) {
+  if (int e = prefill_check("score", p, P, ws, codes, ld_codes, n)) return e;
+  LBWN_REQUIRE(logp, "score: logp is null");
+  LBWN_REQUIRE(scratch, "score: scratch is null");
+  LBWN_REQUIRE((((uintptr_t)scratch) & 15) == 0, "score: scratch %p is not 16-byte aligned", scratch);
+  LBWN_REQUIRE(ld_logp >= n, "score: ld_logp %lld must be >= n = %lld", (long long)ld_logp, (long long)n);
+  // what the head GEMMs and the float4 rows of the log-softmax take
+  LBWN_REQUIRE(p->Cs % 4 == 0 && p->Cp % 4 == 0 && p->Q % 4 == 0 && (p->L * p->Cd) % 4 == 0,
+               "score: n_skip %d, n_post %d, n_quant %d and layers x n_dil %d must be multiples of 4", p->Cs, p->Cp,
+               p->Q, p->L * p->Cd);
+  const long long widest = std::max(std::max((long long)p->L * p->Cd, (long long)p->Cs),
+                                    std::max((long long)p->Cp, (long long)p->Q));
+  LBWN_REQUIRE((long long)p->B * p->pfT * widest < (1LL << 31), "score: batch_sz %d x slice %d x %lld columns >= 2^31",
+               p->B, p->pfT, widest);
+  LBWN_REQUIRE(P->skip && P->post1 && P->post2, "score: SKIP/POST1/POST2 pointers are null");
+  LBWN_REQUIRE(((((uintptr_t)P->skip) | ((uintptr_t)P->post1) | ((uintptr_t)P->post2) | ((uintptr_t)ws)) & 15) == 0,
+               "score: SKIP/POST1/POST2 and the workspace must be 16-byte aligned");
+  size_t off[4], total;
+  score_carve(p, off, total);
+  ScoreRun sc;
+  sc.logp = logp; sc.ld_logp = (long)ld_logp;
+  sc.zcat = gat<float>(scratch, off[0]); sc.S = gat<float>(scratch, off[1]);
+  sc.H = gat<float>(scratch, off[2]); sc.LG = gat<float>(scratch, off[3]);
+  return gen_prefill_run(p, P, ws, codes, ld_codes, n, &sc, (hipStream_t)stream);
 }
 
 // ---- state snapshot ---------------------------------------------------------------------------

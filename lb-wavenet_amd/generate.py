@@ -17,6 +17,10 @@ descending prefix with mass >= top-p; --top-k 1 is greedy decoding.
 --prefill-fanout (build extension; implies the prefill path, needs --teacher-wav) prefills the teacher
 once per distinct voice id and copies that state to every stream of the voice (WaveNetGen.run(...,
 prefill='fanout')); with --mel-npy only the shared [frames, n_lc_in] shape.
+--score-teacher (build extension; needs --teacher-wav, not with --prefill-fanout) handles the teacher as
+--teacher-prefill does, but through WaveNetGen.score: it prints, per stream, the codes scored, the mean
+-log p(code | history) in nats and the bits per sample to stderr, then generation continues as under
+--teacher-prefill.  --score-npy PATH saves the [batch, n] float32 log-probabilities.
 """
 import argparse
 import json
@@ -40,6 +44,12 @@ def get_args(argv=None):
                    help='(build extension) prefill the teacher once per distinct voice id and fan the state '
                         'out to the batch (implies the prefill path; needs --teacher-wav; --mel-npy must be '
                         'the shared [frames, n_lc_in] shape)')
+    p.add_argument('--score-teacher', action='store_true',
+                   help='(build extension) as --teacher-prefill, and print per stream the mean -log p of the '
+                        'teacher\'s codes under the model (nats, and bits per sample) to stderr; needs '
+                        '--teacher-wav, not with --prefill-fanout')
+    p.add_argument('--score-npy', type=str, default=None, metavar='PATH',
+                   help='(build extension) with --score-teacher: save the [batch, n] float32 log-probabilities')
     p.add_argument('--teacher-start', '-ts', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--teacher-duration', '-td', type=float, help='Number of seconds to parse from <teacher_wav>')
     p.add_argument('--gen-seconds', '-g', type=float, default=5, help='Number of additional seconds to generate')
@@ -111,6 +121,15 @@ def main(argv=None):
     if args.prefill_fanout and args.teacher_wav is None:
         print('--prefill-fanout needs --teacher-wav: there is no prompt to prefill', file=stderr)
         sys.exit(1)
+    if args.score_teacher and args.teacher_wav is None:
+        print('--score-teacher needs --teacher-wav: there is no waveform to score', file=stderr)
+        sys.exit(1)
+    if args.score_teacher and args.prefill_fanout:
+        print('--score-teacher scores every stream: it cannot be combined with --prefill-fanout', file=stderr)
+        sys.exit(1)
+    if args.score_npy is not None and not args.score_teacher:
+        print('--score-npy needs --score-teacher', file=stderr)
+        sys.exit(1)
     with open(args.arch_file) as fp:
         arch = normalize_arch(json.load(fp))
     if not os.access(ckpt_file(args.ckpt), os.R_OK):                   # generate.py:43-47
@@ -155,7 +174,16 @@ def main(argv=None):
     ids = [int(v) for v in args.gc_ids.split(',') if v.strip()]
     gc_ids = [ids[i % len(ids)] for i in range(args.batch_size)] if arch['n_gc_embed'] else None
     print('Starting inference...')
-    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel, prefill='fanout' if args.prefill_fanout else args.teacher_prefill)
+    mode = 'fanout' if args.prefill_fanout else 'score' if args.score_teacher else args.teacher_prefill
+    n, wav_streams, wpos = net.run(gen_sz, gc_ids=gc_ids, mel=mel, prefill=mode)
+    if args.score_teacher:
+        logp = net.teacher_logp.cpu().numpy()
+        for i in range(args.batch_size):
+            nats = -float(logp[i].mean())
+            print('score stream {}: {} codes, mean -logp {:.6f} nats, {:.6f} bits per sample'.format(
+                i, logp.shape[1], nats, nats / np.log(2.0)), file=stderr)
+        if args.score_npy is not None:
+            np.save(args.score_npy, logp.astype(np.float32), allow_pickle=False)
     wav_streams = wav_streams.cpu().numpy()
 
     from scipy.io import wavfile

@@ -81,6 +81,9 @@ _SIGS = {
     'lbwn_gen_run': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_int, c_void_p]),
     'lbwn_gen_is_persistent': (c_int, [c_void_p]),
     'lbwn_gen_prefill': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_void_p]),
+    'lbwn_gen_score_scratch_bytes': (c_size_t, [c_void_p]),
+    'lbwn_gen_score': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_fp, c_int64, c_fp,
+                               c_void_p]),
     'lbwn_gen_set_sampling': (c_int, [c_void_p, c_float, c_int, c_float]),
     'lbwn_gen_get_sampling': (c_int, [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_int),
                                       ctypes.POINTER(c_float)]),

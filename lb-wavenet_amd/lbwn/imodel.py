@@ -20,6 +20,10 @@ that way.  On an LC arch the prefilled steps are conditioned on the loaded mel l
 (``init_buffers(mel=...)`` first, or ``run(gen_sz, mel=..., prefill=True)``).  The default teacher
 path is unchanged.
 
+Scoring: ``score(codes)`` is the same parallel pass with the head run over every position
+(lbwn_gen_score): it returns log p(codes[b, j] | history) as float32 [batch_sz, n], advances the state
+as ``prefill(codes)`` does and leaves the last scored step's ``logits()``.
+
 Sampling (keyword-only ``temperature=1.0, top_k=0, top_p=1.0``, or ``set_sampling`` later): the draw of
 every step is filtered as lbwn_gen_set_sampling defines -- top_k keeps the codes whose logit is >= the
 k-th largest (ties kept, 0 = off, >= n_quant = off), the kept codes get e = exp((l - max l) / T), top_p
@@ -148,6 +152,8 @@ class WaveNetGen:
         self._started = False   # init_buffers (lbwn_gen_start) ran on the current plan
         self._state_keep = None   # the snapshot and map of the last load_state: its launch reads them in stream order
         self._fan = None        # (n_voices, n), the private generator of the last fan-out prefill
+        self.teacher_logp = None   # [batch_sz, n] of the last init_buffers(prefill='score')
+        self._score_scratch = None   # (plan, uint8 tensor): lbwn_gen_score's scratch, allocated once per plan
 
     # ---- parameters -------------------------------------------------------------------------
     def load_params(self, src):
@@ -306,6 +312,29 @@ class WaveNetGen:
                                              _lib.stream_ptr()))
         return n
 
+    def score(self, codes):
+        """log p(code | history) of the known waveform ``codes`` (int [n], shared, or [batch_sz, n]) under
+        the model, natural log, as a float32 [batch_sz, n] tensor on the device (lbwn_gen_score): entry
+        [b, j] is the log-probability of codes[b, j] at the step it is fed in.  The state advances exactly as
+        ``prefill(codes)`` advances it, and ``logits()`` holds the last scored step's.  To score without
+        advancing: ``s = save_state(); score(codes); load_state(s)``.  On the current stream."""
+        codes = self._check_codes(codes)
+        if self._plan is None:
+            raise RuntimeError('score: no plan (build_graph and init_buffers first)')
+        if not isinstance(codes, torch.Tensor):
+            codes = torch.from_numpy(np.ascontiguousarray(codes).astype(np.int32))
+        # kept until the next call: the launches read it in stream order
+        self._prefill_codes = codes.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(codes.shape[-1])
+        if self._score_scratch is None or self._score_scratch[0] is not self._plan:   # once per plan
+            nb = self.lib.lbwn_gen_score_scratch_bytes(self._plan)
+            self._score_scratch = (self._plan, torch.empty(nb, dtype=torch.uint8, device=self.device))
+        logp = torch.empty(self.batch_sz, n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lbwn_gen_score(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
+                                           self._prefill_codes.data_ptr(), n if codes.dim() == 2 else 0, n,
+                                           logp.data_ptr(), n, self._score_scratch[1].data_ptr(), _lib.stream_ptr()))
+        return logp
+
     # ---- state ------------------------------------------------------------------------------
     def _state_dims(self):
         return {k: int(self.arch[k]) for k in STATE_DIMS}
@@ -375,9 +404,10 @@ class WaveNetGen:
         return self.load_state(self.save_state(), m)
 
     def _check_prefill(self, prefill, mel):
-        """prefill is False, True or 'fanout'; a fan-out takes a shared (2-D) mel only.  ValueError otherwise."""
-        if prefill not in (False, True, 'fanout'):
-            raise ValueError("prefill must be False, True or 'fanout', got %r" % (prefill,))
+        """prefill is False, True, 'fanout' or 'score'; a fan-out takes a shared (2-D) mel only.  ValueError
+        otherwise."""
+        if prefill not in (False, True, 'fanout', 'score'):
+            raise ValueError("prefill must be False, True, 'fanout' or 'score', got %r" % (prefill,))
         if prefill == 'fanout' and mel is not None and len(tuple(mel.shape)) != 2:
             raise ValueError("prefill='fanout' takes a shared mel [n_frames, n_lc_in] only, got shape %s"
                              % (tuple(mel.shape),))
@@ -415,7 +445,9 @@ class WaveNetGen:
         of steps already taken that way (0 otherwise); on an LC arch the prefilled steps are
         conditioned on the mel this call loads.  ``prefill='fanout'``: the same result for a teacher
         shared by the streams, but the prompt is prefilled once per distinct voice id of ``gc_ids`` (once on
-        an arch without GC) and that state loaded into every stream of the voice; mel absent or 2-D."""
+        an arch without GC) and that state loaded into every stream of the voice; mel absent or 2-D.
+        ``prefill='score'``: as True through ``score``; the teacher's log-probabilities [batch_sz, n] are kept
+        in ``teacher_logp``."""
         self._check_prefill(prefill, mel)
         if prefill and self.teacher_mu is not None:
             self._check_codes(self.teacher_mu, mel_coming=mel is not None)
@@ -452,6 +484,9 @@ class WaveNetGen:
             self.samples()[:, :n] = q
             self.tensor('wav').view(self.batch_sz, self.max_steps)[:, :n] = mu_decode(q, self.arch['n_quant'])
             return n
+        if prefill == 'score' and self.teacher_mu is not None:
+            self.teacher_logp = self.score(self.teacher_mu.reshape(-1)[:self.max_steps])
+            return int(self.teacher_logp.shape[1])
         if prefill and self.teacher_mu is not None:
             return self.prefill(self.teacher_mu.reshape(-1)[:self.max_steps])
         return 0
@@ -488,7 +523,8 @@ class WaveNetGen:
         mel must cover the run, gen_sz <= n_frames·hop + 1.  ``prefill=True``: the teacher's steps
         are prefilled in parallel instead of stepped (the same continuation up to fp32 rounding;
         the waveform then starts with the µ-law-quantised teacher, not the model's ignored draws).
-        ``prefill='fanout'``: as True, the prompt prefilled once per distinct voice id (``init_buffers``)."""
+        ``prefill='fanout'``: as True, the prompt prefilled once per distinct voice id (``init_buffers``).
+        ``prefill='score'``: as True, and ``teacher_logp`` holds the teacher's log-probabilities."""
         self._check_prefill(prefill, mel)
         mel_in = mel
         mel = self._check_mel(mel, int(gen_sz))
