@@ -137,6 +137,68 @@ int lbwn_adam_tf1(float* params, const float* grads, float* m, float* v, int64_t
                   float lr, float beta1, float beta2, float eps, float l2_factor, const float* stats,
                   int64_t* counters, const uint32_t* step_status, void* stream);
 
+/* The same step with global-norm clipping, a guard against non-finite gradients, an exponential
+ * moving average of the weights and a learning-rate schedule, all decided on the device (added
+ * after ABI 5 was declared, same ABI: two symbols added, none altered; lbwn_adam_tf1 keeps its
+ * kernels and its bits).  struct_size = sizeof(this struct), else EINVAL.  The
+ * fields up to step_status mean what lbwn_adam_tf1's arguments mean, with the same refusals.
+ *   t      = counters[2] + 1, read on the device: the t of lr_t.
+ *   g      the gradient Adam sees: with inv = 1/stats[1] (0 if stats[1] == 0), g = fl(raw·inv),
+ *          plus l2_factor·θ on [0, n_weights).
+ *   norm   = sqrt(Σ g²) over all n_total elements (tf.global_norm of the total loss's gradients),
+ *          summed in double in an order that depends on n_total alone: the same bits on every
+ *          device and run, so data-parallel ranks decide alike.  The norm pass (one more launch)
+ *          runs iff clip_norm > 0, skip_nonfinite or info != NULL, and then needs ws.
+ *   scale  = clip_norm / max(norm, clip_norm) with clipping on, else 1; Adam takes g·scale.
+ *   non-finite skip: the norm pass ran, norm is NaN or Inf, and skipping is on (skip_nonfinite, or
+ *          implied by clip_norm > 0).  The step is skipped exactly as a timed-out one: params, m,
+ *          v, ema and counters[0..2] stay bitwise unchanged.  counters[3] is not touched (it
+ *          stays the chain status); instead *nonfinite_skips += 1.  (Squares are formed in
+ *          double: finite gradients whose squares overflow fp32 do not skip.)
+ *   status skip: a nonzero *step_status skips as in lbwn_adam_tf1, is ORed into counters[3] and
+ *          does not count as a non-finite skip.
+ *   lr     lr_eff = lr·w·r, in double on the device: w = min(1, t / lr_warmup_steps) with warmup
+ *          on, else 1; r = lr_decay_rate^(t / lr_decay_steps) with decay on, else 1, the exponent
+ *          floor(t / lr_decay_steps) with lr_decay_staircase (tf.train.exponential_decay with
+ *          global_step = t).  Then lr_t = lr_eff·√(1-β2^t)/(1-β1^t).  A skipped step does not
+ *          advance t, so the schedule waits with it.
+ *   ema    after the element's update, in the same kernel and pass: shadow -= (1 - d_t)·(shadow -
+ *          θ_new), d_t = min(ema_decay, (1+t)/(10+t)) with ema_num_updates, else ema_decay
+ *          (tf.train.ExponentialMovingAverage with num_updates = t).  The caller initialises the
+ *          shadow, from the parameters.
+ *   info   (nullable) written by one thread on every call: [0] norm before clipping, [1] the scale
+ *          applied, [2] 1 if the step was skipped as non-finite else 0, [3] lr_eff.  On a status
+ *          skip [0..2] are 0.
+ * As lbwn_adam_tf1, the counters (and the skip count) advance only when stats is given.
+ * Stream-ordered, no host synchronisation or allocation, graph-capturable.  With every option
+ * neutral (no norm pass, ema_decay 0, no schedule) the call launches what lbwn_adam_tf1 launches.
+ * EINVAL before any launch, naming the argument: lbwn_adam_tf1's refusals, a wrong struct_size,
+ * clip_norm negative or not finite, ema_decay outside [0, 1), ema NULL or misaligned with
+ * ema_decay > 0, ws NULL or misaligned when the norm pass runs, negative step counts,
+ * lr_decay_rate outside (0, 1] with decay on. */
+typedef struct lbwn_adam_ex_args {
+  size_t struct_size;
+  float* params; const float* grads; float* m; float* v;
+  int64_t n_weights, n_total;
+  float lr, beta1, beta2, eps, l2_factor;
+  const float* stats; int64_t* counters; const uint32_t* step_status;   /* as lbwn_adam_tf1 */
+  float clip_norm;            /* 0 = off; else finite and > 0 */
+  int skip_nonfinite;         /* clip_norm > 0 implies it */
+  float ema_decay;            /* 0 = off; else in (0, 1) */
+  int ema_num_updates;        /* 1: d_t = min(ema_decay, (1+t)/(10+t)); 0: d_t = ema_decay */
+  float* ema;                 /* [n_total] shadow, required iff ema_decay > 0, 16-B aligned */
+  int64_t lr_warmup_steps;    /* 0 = off */
+  int64_t lr_decay_steps;     /* 0 = off */
+  float lr_decay_rate;        /* in (0, 1] when lr_decay_steps > 0 */
+  int lr_decay_staircase;
+  float* ws;                  /* lbwn_adam_ex_ws_floats(n_total) floats, 16-B aligned; required when the norm pass runs */
+  float* info;                /* nullable device fp32[4] out */
+  int64_t* nonfinite_skips;   /* nullable device counter */
+} lbwn_adam_ex_args;
+/* Floats of ws for n_total elements (0 for n_total < 1; never shrinks as n_total grows). */
+int64_t lbwn_adam_ex_ws_floats(int64_t n_total);
+int lbwn_adam_ex(const lbwn_adam_ex_args* a, void* stream);
+
 /* ---- cached autoregressive generation (imodel.WaveNetGen, imodel.py:7-303) ------------ */
 typedef struct lbwn_gen_plan lbwn_gen_plan;
 /* B streams, outputs for up to max_steps samples, teacher vector up to max_teacher codes.

@@ -35,6 +35,57 @@ int lbwn_adam_tf1(float* params, const float* grads, float* m, float* v, int64_t
   return 0;
 }
 
+int64_t lbwn_adam_ex_ws_floats(int64_t n_total) { return (int64_t)lbwn_adam_ex_ws_floats_impl((long)n_total); }
+
+int lbwn_adam_ex(const lbwn_adam_ex_args* a, void* stream) {
+  LBWN_REQUIRE(a != nullptr, "adam_ex: null argument struct");
+  LBWN_REQUIRE(a->struct_size == sizeof(lbwn_adam_ex_args), "adam_ex: struct_size %zu != %zu (another ABI?)",
+               a->struct_size, sizeof(lbwn_adam_ex_args));
+  LBWN_REQUIRE(a->params && a->grads && a->m && a->v && a->counters, "adam_ex: null argument");
+  LBWN_REQUIRE(a->n_weights >= 0 && a->n_weights <= a->n_total, "adam_ex: bad sizes");
+  LBWN_REQUIRE(a->clip_norm >= 0.f && a->clip_norm <= 3.402823466e38f, "adam_ex: clip_norm must be 0 (off) or finite and > 0");
+  LBWN_REQUIRE(a->ema_decay >= 0.f && a->ema_decay < 1.f, "adam_ex: ema_decay must be 0 (off) or in (0, 1)");
+  const bool has_ema = a->ema_decay > 0.f;
+  LBWN_REQUIRE(!has_ema || (a->ema && !((uintptr_t)a->ema & 15)),
+               "adam_ex: ema must be a 16-byte aligned [n_total] buffer when ema_decay > 0");
+  LBWN_REQUIRE(a->lr_warmup_steps >= 0, "adam_ex: lr_warmup_steps must be >= 0");
+  LBWN_REQUIRE(a->lr_decay_steps >= 0, "adam_ex: lr_decay_steps must be >= 0");
+  LBWN_REQUIRE(a->lr_decay_steps == 0 || (a->lr_decay_rate > 0.f && a->lr_decay_rate <= 1.f),
+               "adam_ex: lr_decay_rate must be in (0, 1] when lr_decay_steps > 0");
+  const bool norm_pass = a->clip_norm > 0.f || a->skip_nonfinite || a->info != nullptr;
+  LBWN_REQUIRE(!norm_pass || (a->ws && !((uintptr_t)a->ws & 15)),
+               "adam_ex: ws must be a 16-byte aligned buffer of lbwn_adam_ex_ws_floats(n_total) floats when "
+               "clip_norm, skip_nonfinite or info asks for the norm");
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned* ss = (const unsigned*)a->step_status;
+  const bool sched = a->lr_warmup_steps > 0 || a->lr_decay_steps > 0;
+  if (!norm_pass && !has_ema && !sched) {   // every option neutral: the launches of lbwn_adam_tf1
+    int e = lbwn_adam_launch2(a->params, a->grads, a->m, a->v, (long)a->n_weights, (long)a->n_total, a->lr, a->beta1,
+                              a->beta2, a->eps, a->l2_factor, a->stats, (const long long*)a->counters, ss, st);
+    if (e) return e;
+    if (a->stats) return lbwn_counters_launch((long long*)a->counters, a->stats, 1, ss, st);
+    return 0;
+  }
+  lbwn_adam_ex_dev d;
+  memset(&d, 0, sizeof(d));
+  d.p = a->params; d.gr = a->grads; d.m = a->m; d.v = a->v;
+  d.nw = (long)a->n_weights; d.n = (long)a->n_total;
+  d.lr = a->lr; d.b1 = a->beta1; d.b2 = a->beta2; d.eps = a->eps; d.l2 = a->l2_factor;
+  d.stats = a->stats; d.counters = (const long long*)a->counters; d.status = ss;
+  d.clip = a->clip_norm; d.skip_nonfinite = a->skip_nonfinite ? 1 : 0;
+  d.ema_decay = a->ema_decay; d.ema_num_updates = a->ema_num_updates ? 1 : 0; d.ema = has_ema ? a->ema : nullptr;
+  d.warmup = (long)a->lr_warmup_steps; d.decay_steps = (long)a->lr_decay_steps;
+  d.decay_rate = a->lr_decay_rate; d.staircase = a->lr_decay_staircase ? 1 : 0;
+  d.info = a->info;
+  const unsigned* decision = nullptr;
+  int e = lbwn_adam_ex_launch(d, a->ws, norm_pass, st, &decision);
+  if (e) return e;
+  if (a->stats)
+    return lbwn_counters_launch((long long*)a->counters, a->stats, 1, ss, st, decision,
+                                (long long*)a->nonfinite_skips);
+  return 0;
+}
+
 int lbwn_mulaw_encode(const float* x, int* q, int64_t n, int n_quanta, int tf32, void* stream) {
   LBWN_REQUIRE(n >= 0 && n_quanta >= 2, "mulaw_encode: bad arguments");
   if (n == 0) return 0;

@@ -256,8 +256,29 @@ int lbwn_sum_bias_launch(const float* b, int L, int N, float* out, hipStream_t s
 int lbwn_adam_launch2(float* params, const float* grads, float* m, float* v, long n_weights, long n_total,
                       float lr, float b1, float b2, float eps, float l2, const float* stats,
                       const long long* counters, const unsigned* status, hipStream_t st);
+// nonfinite (nullable): the decision word lbwn_adam_ex_launch's update left; set = count the step in
+// *nonfinite_skips (nullable) and advance nothing
 int lbwn_counters_launch(long long* counters, const float* stats, int adam_applied, const unsigned* status,
-                         hipStream_t st);
+                         hipStream_t st, const unsigned* nonfinite = nullptr, long long* nonfinite_skips = nullptr);
+// The extended Adam step (include/lbwn.h lbwn_adam_ex; arguments checked by the caller).  part,
+// nparts and decision are carved from ws by the launcher.
+struct lbwn_adam_ex_dev {
+  float* p; const float* gr; float* m; float* v;
+  long nw, n;
+  float lr, b1, b2, eps, l2;
+  const float* stats; const long long* counters; const unsigned* status;
+  float clip;           // 0 = no clipping
+  int skip_nonfinite;
+  float ema_decay; int ema_num_updates; float* ema;   // ema == nullptr: no EMA
+  long warmup, decay_steps; float decay_rate; int staircase;
+  const double* part; int nparts; unsigned* decision;
+  float* info;
+};
+int lbwn_adam_ex_nparts(long n);
+long lbwn_adam_ex_ws_floats_impl(long n);
+// norm_pass: run the Σ g² launch first (ws holds lbwn_adam_ex_ws_floats_impl(n) floats).
+// *decision: the word for lbwn_counters_launch's `nonfinite` (nullptr without the norm pass)
+int lbwn_adam_ex_launch(lbwn_adam_ex_dev a, float* ws, bool norm_pass, hipStream_t st, const unsigned** decision);
 // dPRE = onehot(q)ᵀ·dx0 as an LDS-histogram scatter + fixed-order reduction; dPRE_B = Σ dx0 (nullable);
 // dx0[m] = g[m] + (t+gd < T ? dprev[m+gd] : 0) formed on the fly
 int lbwn_pre_grad_ws_floats(int Q, int Cr);

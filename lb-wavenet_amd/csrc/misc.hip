@@ -461,6 +461,50 @@ LBWN_DEV float adam_elem(float th, float g, float& m, float& v, float lr_t, floa
 
 // Four elements per thread as dwordx4 loads and stores (the flat buffers are 16-B aligned, checked
 // by the launcher); the n % 4 tail elements one per thread.  HBM-bound: 28 B per parameter.
+// HAS_SCALE: Adam takes g·scale (global-norm clipping); HAS_EMA: the shadow follows the element's
+// new value in the same pass, shadow -= omd·(shadow - θ_new) (8 more bytes per parameter).  Each
+// is compiled in only where asked for, so <false, false> is the plain TF1 step instruction for
+// instruction (hipcc contracts a·b + c per kernel).
+template <bool HAS_SCALE, bool HAS_EMA>
+LBWN_DEV void adam_loop(float* __restrict__ p, const float* __restrict__ gr, float* __restrict__ m,
+                        float* __restrict__ v, long nw, long n, float lr_t, float inv, float b1, float b2, float eps,
+                        float l2, float scale, float* __restrict__ ema, float omd) {
+  const long n4 = n >> 2;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const floatx4 th = ((const floatx4*)p)[i];
+    floatx4 g = ((const floatx4*)gr)[i];
+    floatx4 mm = ((const floatx4*)m)[i], vv = ((const floatx4*)v)[i], out;
+    floatx4 sh;
+    if (HAS_EMA) sh = ((const floatx4*)ema)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gj = g[j] * inv;
+      if (4 * i + j < nw) gj += l2 * th[j];
+      if (HAS_SCALE) gj *= scale;
+      float mj = mm[j], vj = vv[j];
+      out[j] = adam_elem(th[j], gj, mj, vj, lr_t, b1, b2, eps);
+      mm[j] = mj;
+      vv[j] = vj;
+      if (HAS_EMA) sh[j] -= omd * (sh[j] - out[j]);
+    }
+    ((floatx4*)m)[i] = mm;
+    ((floatx4*)v)[i] = vv;
+    ((floatx4*)p)[i] = out;
+    if (HAS_EMA) ((floatx4*)ema)[i] = sh;
+  }
+  const long e = 4 * n4 + blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (e < n) {
+    float g = gr[e] * inv;
+    if (e < nw) g += l2 * p[e];
+    if (HAS_SCALE) g *= scale;
+    float mj = m[e], vj = v[e];
+    p[e] = adam_elem(p[e], g, mj, vj, lr_t, b1, b2, eps);
+    m[e] = mj;
+    v[e] = vj;
+    if (HAS_EMA) ema[e] -= omd * (ema[e] - p[e]);
+  }
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ gr,
                                                    float* __restrict__ m, float* __restrict__ v, long nw, long n,
                                                    float lr, float b1, float b2, float eps, float l2,
@@ -470,43 +514,126 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const double t = (double)(counters[2] + 1);
   const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
   const float inv = stats ? (stats[1] > 0.f ? 1.f / stats[1] : 0.f) : 1.f;
+  adam_loop<false, false>(p, gr, m, v, nw, n, lr_t, inv, b1, b2, eps, l2, 1.f, nullptr, 0.f);
+}
+
+// ---- the extended step (lbwn_adam_ex): global-norm clipping, non-finite skip, EMA, LR schedule ----
+// Pass 1: Σ g² with g exactly the gradient Adam sees (f32 raw·inv, + l2·θ on the weight region),
+// squared and summed in double.  The grid is lbwn_adam_ex_nparts(n) blocks, a function of n alone;
+// a thread adds its grid-stride elements in index order, the block's 256 sums meet in a fixed LDS
+// tree and the block stores one double: no atomics, so the partials are the same bits on every
+// device and in every run.  HBM-bound (8 B per weight, 4 B per bias).
+constexpr int AX_PARTS = 512;
+
+// 256 doubles summed by halving strides; every thread returns the total
+LBWN_DEV double block_sum256(double s, double* sh) {
+  sh[threadIdx.x] = s;
+  __syncthreads();
+#pragma unroll
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__global__ __launch_bounds__(256) void adam_sumsq_kernel(const float* __restrict__ p, const float* __restrict__ gr,
+                                                         long nw, long n, float l2, const float* stats,
+                                                         double* __restrict__ part) {
+  __shared__ double sh[256];
+  const float inv = stats ? (stats[1] > 0.f ? 1.f / stats[1] : 0.f) : 1.f;
   const long n4 = n >> 2;
+  double s = 0.0;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const floatx4 th = ((const floatx4*)p)[i];
-    floatx4 g = ((const floatx4*)gr)[i];
-    floatx4 mm = ((const floatx4*)m)[i], vv = ((const floatx4*)v)[i], out;
+    const floatx4 g = ((const floatx4*)gr)[i];
+    floatx4 th = {0.f, 0.f, 0.f, 0.f};
+    if (4 * i < nw) th = ((const floatx4*)p)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float gj = g[j] * inv;
       if (4 * i + j < nw) gj += l2 * th[j];
-      float mj = mm[j], vj = vv[j];
-      out[j] = adam_elem(th[j], gj, mj, vj, lr_t, b1, b2, eps);
-      mm[j] = mj;
-      vv[j] = vj;
+      s += (double)gj * (double)gj;
     }
-    ((floatx4*)m)[i] = mm;
-    ((floatx4*)v)[i] = vv;
-    ((floatx4*)p)[i] = out;
   }
   const long e = 4 * n4 + blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (e < n) {
     float g = gr[e] * inv;
     if (e < nw) g += l2 * p[e];
-    float mj = m[e], vj = v[e];
-    p[e] = adam_elem(p[e], g, mj, vj, lr_t, b1, b2, eps);
-    m[e] = mj;
-    v[e] = vj;
+    s += (double)g * (double)g;
   }
+  const double tot = block_sum256(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// Pass 2: every block sums the partials in the same fixed order (so all hold the same bits), forms
+// scale, the scheduled lr and the EMA step, and updates its elements.  Block 0 leaves the
+// non-finite decision in *a.decision for counters_kernel (next in stream order) and writes info.
+template <bool HAS_SCALE, bool HAS_EMA>
+__global__ __launch_bounds__(256) void adam_ex_kernel(lbwn_adam_ex_dev a) {
+  __shared__ double sh[256];
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  const double t = (double)(a.counters[2] + 1);
+  double lr_eff = (double)a.lr;
+  if (a.warmup > 0) lr_eff *= fmin(1.0, t / (double)a.warmup);
+  if (a.decay_steps > 0) {
+    double ex = t / (double)a.decay_steps;
+    if (a.staircase) ex = floor(ex);
+    lr_eff *= pow((double)a.decay_rate, ex);
+  }
+  if (a.status && *a.status) {   // the chain status skips as in adam_kernel; not a non-finite skip
+    if (lead) {
+      if (a.decision) *a.decision = 0u;
+      if (a.info) {
+        a.info[0] = 0.f; a.info[1] = 0.f; a.info[2] = 0.f; a.info[3] = (float)lr_eff;
+      }
+    }
+    return;
+  }
+  double norm = 0.0;
+  float scale = 1.f;
+  bool skip = false;
+  if (a.part) {   // uniform over the grid
+    double s = 0.0;
+    for (int k = threadIdx.x; k < a.nparts; k += 256) s += a.part[k];
+    const double sum = block_sum256(s, sh);
+    norm = sqrt(sum);
+    skip = (HAS_SCALE || a.skip_nonfinite) && !(fabs(norm) <= 1.7976931348623157e308);
+    if (HAS_SCALE && !skip) scale = (float)((double)a.clip / fmax(norm, (double)a.clip));
+  }
+  if (lead) {
+    if (a.decision) *a.decision = skip ? 1u : 0u;
+    if (a.info) {
+      a.info[0] = (float)norm; a.info[1] = scale; a.info[2] = skip ? 1.f : 0.f; a.info[3] = (float)lr_eff;
+    }
+  }
+  if (skip) return;
+  const float lr_t = (float)(lr_eff * sqrt(1.0 - pow((double)a.b2, t)) / (1.0 - pow((double)a.b1, t)));
+  const float inv = a.stats ? (a.stats[1] > 0.f ? 1.f / a.stats[1] : 0.f) : 1.f;
+  float omd = 0.f;
+  if (HAS_EMA) {
+    double d = (double)a.ema_decay;
+    if (a.ema_num_updates) d = fmin(d, (1.0 + t) / (10.0 + t));
+    omd = (float)(1.0 - d);
+  }
+  adam_loop<HAS_SCALE, HAS_EMA>(a.p, a.gr, a.m, a.v, a.nw, a.n, lr_t, inv, a.b1, a.b2, a.eps, a.l2, scale, a.ema,
+                                omd);
 }
 
 // counters: [0] GLOBAL_STEP, [1] VALID_SAMPLES, [2] Adam t-1 (tmodel.py:282-287), [3] the
 // cumulative status: every step's status word ORed in (never reset by a step), so one read
 // after many steps tells whether any of them timed out.  A failed step advances nothing else.
-__global__ void counters_kernel(long long* counters, const float* stats, int adam_applied, const unsigned* status) {
+__global__ void counters_kernel(long long* counters, const float* stats, int adam_applied, const unsigned* status,
+                                const unsigned* nonfinite, long long* nonfinite_skips) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     const unsigned s = status ? *status : 0u;
     if (s) {
       counters[3] |= (long long)s;
+      return;
+    }
+    // the extended step's non-finite skip (adam_ex_kernel's decision word; nullptr = none): counted
+    // apart from the chain status, which counters[3] alone keeps
+    if (nonfinite && *nonfinite) {
+      if (nonfinite_skips) *nonfinite_skips += 1;
       return;
     }
     counters[0] += 1;
@@ -699,8 +826,38 @@ int lbwn_adam_launch2(float* params, const float* grads, float* m, float* v, lon
 }
 
 int lbwn_counters_launch(long long* counters, const float* stats, int adam_applied, const unsigned* status,
-                         hipStream_t st) {
-  counters_kernel<<<1, 64, 0, st>>>(counters, stats, adam_applied, status);
+                         hipStream_t st, const unsigned* nonfinite, long long* nonfinite_skips) {
+  counters_kernel<<<1, 64, 0, st>>>(counters, stats, adam_applied, status, nonfinite, nonfinite_skips);
+  LBWN_CHECK_LAUNCH();
+  return 0;
+}
+
+// The partial count of the norm pass: a function of n alone (the sums' order must not depend on the device).
+int lbwn_adam_ex_nparts(long n) { return n < 1 ? 0 : grid_for(std::max(n / 4, 1L), 256, AX_PARTS); }
+
+// the partials as doubles, then the decision word (padded to 16 B)
+long lbwn_adam_ex_ws_floats_impl(long n) { return n < 1 ? 0 : 2L * lbwn_adam_ex_nparts(n) + 4; }
+
+int lbwn_adam_ex_launch(lbwn_adam_ex_dev a, float* ws, bool norm_pass, hipStream_t st, const unsigned** decision) {
+  LBWN_REQUIRE(!(((uintptr_t)a.p | (uintptr_t)a.gr | (uintptr_t)a.m | (uintptr_t)a.v) & 15),
+               "adam: parameter, gradient and slot buffers must be 16-byte aligned");
+  a.part = nullptr;
+  a.nparts = 0;
+  a.decision = nullptr;
+  if (norm_pass && a.n >= 1) {
+    a.nparts = lbwn_adam_ex_nparts(a.n);
+    a.part = (double*)ws;
+    a.decision = (unsigned*)(ws + 2L * a.nparts);
+    adam_sumsq_kernel<<<a.nparts, 256, 0, st>>>(a.p, a.gr, a.nw, a.n, a.l2, a.stats, (double*)ws);
+    LBWN_CHECK_LAUNCH();
+  }
+  *decision = a.decision;
+  const int grid = grid_for(std::max(a.n / 4, 1L), 256, 4096);
+  const bool hs = a.clip > 0.f, he = a.ema != nullptr;
+  if (hs && he) adam_ex_kernel<true, true><<<grid, 256, 0, st>>>(a);
+  else if (hs) adam_ex_kernel<true, false><<<grid, 256, 0, st>>>(a);
+  else if (he) adam_ex_kernel<false, true><<<grid, 256, 0, st>>>(a);
+  else adam_ex_kernel<false, false><<<grid, 256, 0, st>>>(a);
   LBWN_CHECK_LAUNCH();
   return 0;
 }

@@ -21,6 +21,8 @@ prefill='fanout')); with --mel-npy only the shared [frames, n_lc_in] shape.
 --teacher-prefill does, but through WaveNetGen.score: it prints, per stream, the codes scored, the mean
 -log p(code | history) in nats and the bits per sample to stderr, then generation continues as under
 --teacher-prefill.  --score-npy PATH saves the [batch, n] float32 log-probabilities.
+--ema (build extension) loads every variable from its exponential moving average in the checkpoint
+(train.py --ema-decay); a checkpoint without them is an error.
 """
 import argparse
 import json
@@ -73,6 +75,9 @@ def get_args(argv=None):
     p.add_argument('--top-p', type=float, default=1.0,
                    help='(build extension) nucleus sampling: draw among the most likely codes whose mass '
                         'reaches p, in (0, 1] (1 = off); applied after --top-k')
+    p.add_argument('--ema', action='store_true',
+                   help='(build extension) generate from the averaged weights the checkpoint holds '
+                        '(<var>/ExponentialMovingAverage, written by train.py --ema-decay)')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('ckpt', metavar='CHECKPOINT_PREFIX', type=str)
     p.add_argument('wav_dir', metavar='OUTPUT_WAV_DIR', type=str)
@@ -169,7 +174,13 @@ def main(argv=None):
                      top_k=args.top_k, top_p=args.top_p)
     print('Building graph.')
     print('Restoring from {}'.format(args.ckpt))
-    net.restore(args.ckpt)
+    try:
+        net.restore(args.ckpt, ema=args.ema)
+    except ValueError as e:
+        if not args.ema:
+            raise
+        print('--ema: {}'.format(e), file=stderr)
+        sys.exit(1)
     print('Initializing buffers.')
     ids = [int(v) for v in args.gc_ids.split(',') if v.strip()]
     gc_ids = [ids[i % len(ids)] for i in range(args.batch_size)] if arch['n_gc_embed'] else None

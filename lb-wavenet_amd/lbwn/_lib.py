@@ -56,6 +56,22 @@ class GemmExArgs(ctypes.Structure):
         self.struct_size = ctypes.sizeof(GemmExArgs)
 
 
+class AdamExArgs(ctypes.Structure):
+    """lbwn_adam_ex_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('params', c_fp), ('grads', c_fp), ('m', c_fp), ('v', c_fp),
+                ('n_weights', c_int64), ('n_total', c_int64),
+                ('lr', c_float), ('beta1', c_float), ('beta2', c_float), ('eps', c_float), ('l2_factor', c_float),
+                ('stats', c_fp), ('counters', c_fp), ('step_status', c_fp),
+                ('clip_norm', c_float), ('skip_nonfinite', c_int), ('ema_decay', c_float), ('ema_num_updates', c_int),
+                ('ema', c_fp), ('lr_warmup_steps', c_int64), ('lr_decay_steps', c_int64),
+                ('lr_decay_rate', c_float), ('lr_decay_staircase', c_int),
+                ('ws', c_fp), ('info', c_fp), ('nonfinite_skips', c_fp)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(AdamExArgs)
+
+
 _SIGS = {
     'lbwn_last_error': (ctypes.c_char_p, []),
     'lbwn_abi_version': (c_int, []),
@@ -71,6 +87,8 @@ _SIGS = {
                                     c_fp, c_void_p]),
     'lbwn_adam_tf1': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int64, c_int64, c_float, c_float, c_float, c_float,
                               c_float, c_fp, c_fp, c_fp, c_void_p]),
+    'lbwn_adam_ex_ws_floats': (c_int64, [c_int64]),
+    'lbwn_adam_ex': (c_int, [ctypes.POINTER(AdamExArgs), c_void_p]),
     'lbwn_gen_plan_create': (c_int, [ctypes.POINTER(Arch), c_int, c_int64, c_int64, ctypes.POINTER(c_void_p)]),
     'lbwn_gen_plan_destroy': (None, [c_void_p]),
     'lbwn_gen_workspace_bytes': (c_size_t, [c_void_p]),

@@ -156,21 +156,31 @@ class WaveNetGen:
         self._score_scratch = None   # (plan, uint8 tensor): lbwn_gen_score's scratch, allocated once per plan
 
     # ---- parameters -------------------------------------------------------------------------
-    def load_params(self, src):
-        """src: WaveNetTrain, {serial name: tensor/array}, or a flat tensor of this layout."""
+    def load_params(self, src, ema=False):
+        """src: WaveNetTrain, {serial name: tensor/array}, or a flat tensor of this layout.  With
+        ``ema`` (a {name: tensor} source only) every variable is taken from its averaged shadow,
+        '<name>/ExponentialMovingAverage' (lbwn.optim.AdamOptimizer(ema_decay=...) saves them); a
+        ValueError names the first one the source lacks."""
         with torch.no_grad():
             if hasattr(src, 'vars'):
                 src = src.vars
             if isinstance(src, torch.Tensor):
+                if ema:
+                    raise ValueError('ema: a flat tensor holds no shadows; pass the checkpoint\'s {name: tensor}')
                 self.flat.copy_(src)
                 return
+            sfx = '/ExponentialMovingAverage' if ema else ''
+            for name in self.vars:
+                if ema and name + sfx not in src:
+                    raise ValueError('ema: the checkpoint has no %s (was it trained with ema_decay?)' % (name + sfx))
             for name, v in self.vars.items():
-                v.copy_(torch.as_tensor(np.asarray(src[name]) if not isinstance(src[name], torch.Tensor)
-                                        else src[name], dtype=torch.float32))
+                t = src[name + sfx]
+                v.copy_(torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t,
+                                        dtype=torch.float32))
 
-    def restore(self, path):
+    def restore(self, path, ema=False):
         from .ckpt import load_tensors
-        self.load_params(load_tensors(path))
+        self.load_params(load_tensors(path), ema=ema)
 
     # ---- graph ------------------------------------------------------------------------------
     def build_graph(self, max_steps):

@@ -10,6 +10,12 @@ Multi-GPU: launch with torch.distributed.run (one process per GPU); --batch-size
 the per-GPU batch, the dealer runs over the global batch and each rank trains on its rows,
 gradients are summed over ranks before the (replicated) Adam step (lbwn.dist).
 
+Build extensions of the optimizer step, all decided on the device (lbwn_adam_ex): --clip-norm,
+--skip-nonfinite, --ema-decay, --lr-warmup-steps, --lr-decay-steps, --lr-decay-rate, --log-grad-norm;
+each overrides the PAR_FILE key of the same name (clip_norm, ..., log_grad_norm; all optional).  With
+clipping or --log-grad-norm a second line follows each progress line:
+grad_norm, scale, lr and nonfinite_skips of the last applied step.
+
 TF-only switches are accepted for command-line compatibility: --tf-eager is implied,
 --add-summary/--tb-dir/--prof-dir/--timeline-file print what replaces them (rocprofv3),
 --tf-debug and --cpu-only exit(1) (there is no CPU execution path).
@@ -50,6 +56,21 @@ def get_args(argv=None):
     p.add_argument('--num-global-cond', '-gc', type=int, metavar='INT',
                    help='Number of global conditioning categories')
     p.add_argument('--seed', type=int, default=None, help='(build extension) weight / shuffle seed')
+    p.add_argument('--clip-norm', type=float, metavar='FLOAT',
+                   help='(build extension) clip the gradient to this global norm, on the device (0 = off)')
+    p.add_argument('--skip-nonfinite', action='store_true', default=None,
+                   help='(build extension) leave a step whose gradient norm is NaN/Inf unapplied and count it '
+                        '(implied by --clip-norm)')
+    p.add_argument('--ema-decay', type=float, metavar='FLOAT',
+                   help='(build extension) keep an exponential moving average of the weights, decay in (0, 1); '
+                        'saved as <var>/ExponentialMovingAverage (generate.py --ema)')
+    p.add_argument('--lr-warmup-steps', type=int, metavar='INT',
+                   help='(build extension) linear learning-rate warmup over this many Adam steps')
+    p.add_argument('--lr-decay-steps', type=int, metavar='INT',
+                   help='(build extension) exponential decay: lr * rate^(t / steps)')
+    p.add_argument('--lr-decay-rate', type=float, metavar='FLOAT', help='(build extension) its rate, in (0, 1]')
+    p.add_argument('--log-grad-norm', action='store_true', default=None,
+                   help='(build extension) print the gradient norm with the progress line, without clipping')
     p.add_argument('ckpt_path', type=str, metavar='CKPT_PATH_PFX')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('par_file', type=str, metavar='PAR_FILE')
@@ -67,6 +88,27 @@ def prepare_arch(arch, num_global_cond):
     except ArchError as e:
         print(str(e), file=sys.stderr)
         sys.exit(1)
+
+
+OPT_KEYS = ('clip_norm', 'skip_nonfinite', 'ema_decay', 'lr_warmup_steps', 'lr_decay_steps', 'lr_decay_rate',
+            'log_grad_norm')
+
+
+def override_par(args, par):
+    """Command-line values replace the PAR_FILE's keys of the same name (a flag not given leaves the key)."""
+    for flag, key in (('batch_size', 'batch_sz'), ('slice_size', 'slice_sz'), ('l2_factor', 'l2_factor'),
+                      ('learning_rate', 'learning_rate')) + tuple((k, k) for k in OPT_KEYS):
+        if getattr(args, flag) is not None:
+            par[key] = getattr(args, flag)
+    return par
+
+
+def optimizer_kwargs(par):
+    """AdamOptimizer's arguments from the par dict; the optional keys are read with .get."""
+    return dict(learning_rate=par['learning_rate'], clip_norm=par.get('clip_norm') or None,
+                skip_nonfinite=bool(par.get('skip_nonfinite', False)), ema_decay=par.get('ema_decay') or None,
+                warmup_steps=par.get('lr_warmup_steps', 0), decay_steps=par.get('lr_decay_steps', 0),
+                decay_rate=par.get('lr_decay_rate', 1.0), log_norm=bool(par.get('log_grad_norm', False)))
 
 
 def main(argv=None):
@@ -97,14 +139,7 @@ def main(argv=None):
                   '`rocprofv3 --kernel-trace --stats -- python train.py ...`'.format(flag.replace('_', '-')),
                   file=stderr)
 
-    if args.batch_size is not None:
-        par['batch_sz'] = args.batch_size
-    if args.slice_size is not None:
-        par['slice_sz'] = args.slice_size
-    if args.l2_factor is not None:
-        par['l2_factor'] = args.l2_factor
-    if args.learning_rate is not None:
-        par['learning_rate'] = args.learning_rate
+    override_par(args, par)
 
     import torch
     from lbwn import dist as lbdist
@@ -139,13 +174,21 @@ def main(argv=None):
     dset.set_receptive_field_size(net.get_recep_field_sz())
     dset.build()
     dset.init_vars()
-    optimizer = AdamOptimizer(learning_rate=par['learning_rate'])
+    try:
+        optimizer = AdamOptimizer(**optimizer_kwargs(par))
+    except ValueError as e:
+        print('Error: {}'.format(e), file=stderr)
+        sys.exit(1)
+    log_norm = optimizer.norm_pass and dp.rank == 0
+    skips_seen = 0
     print('Built graph.', file=stderr)
 
     if args.resume_step:
         net.restore(optimizer)
         dset.restore()
         print('Restored net and dset from checkpoint', file=stderr)
+        if log_norm:
+            skips_seen = optimizer.nonfinite_skips(net)
     dp.broadcast_params(net)
 
     print('Starting training...', file=stderr)
@@ -161,6 +204,17 @@ def main(argv=None):
         if args.progress_interval and net.global_step_host % args.progress_interval == 0:
             net.check_status()                # cumulative: any timed-out step since the start (never applied)
         net.maybe_print()                     # tmodel.py:272-281 prints before the step counters advance
+        if (log_norm and args.progress_interval and net.global_step_host % args.progress_interval == 0
+                and step > (args.resume_step or 1)):
+            # the last applied step's norm; the progress line above has synchronised already
+            info = optimizer.grad_info(net).tolist()
+            skips = optimizer.nonfinite_skips(net)
+            print('grad_norm\t%.4g\tscale\t%.4g\tlr\t%.4g\tnonfinite_skips\t%d' % (info[0], info[1], info[3], skips),
+                  file=stderr)
+            if skips > skips_seen:
+                print('Warning: {} more step(s) had a non-finite gradient norm and were not applied'.format(
+                    skips - skips_seen), file=stderr)
+                skips_seen = skips
         optimizer.apply(net)
         if step % args.save_interval == 0 and step != args.resume_step:
             net.check_status()
