@@ -59,7 +59,9 @@ int lbwn_abi_version(void);
 /* ---- plan: the WaveNetTrain graph for a fixed (arch, batch_sz, slice_sz) ------------ */
 typedef struct lbwn_plan lbwn_plan;
 /* replaces WaveNetTrain.__init__ + build() graph construction (tmodel.py:8-48, :292-340).
- * n_quant is a multiple of 4; lbwn_train_backward takes n_quant <= 1024 (EINVAL beyond). */
+ * n_quant is a multiple of 4; lbwn_train_backward takes n_quant <= 1024 (EINVAL beyond).
+ * n_blocks >= 1, n_block_layers in 1..16, batch_sz >= 1, slice_sz >= 2 and
+ * batch_sz * slice_sz >= 4 positions (EINVAL below: the bf16-split GEMMs take no fewer than 4 rows). */
 int lbwn_plan_create(const lbwn_arch* arch, int batch_sz, int slice_sz, lbwn_plan** out);
 void lbwn_plan_destroy(lbwn_plan* plan);
 size_t lbwn_plan_workspace_bytes(const lbwn_plan* plan);

@@ -311,6 +311,10 @@ int lbwn_plan_create(const lbwn_arch* a, int B, int T, lbwn_plan** out) {
   LBWN_REQUIRE(a->n_skip >= 1 && a->n_post >= 1 && a->n_quant % 4 == 0,
                "plan: n_skip/n_post >= 1 and n_quant a multiple of 4 required");
   LBWN_REQUIRE(B >= 1 && T >= 2, "plan: batch_sz >= 1 and slice_sz >= 2 required");
+  // the bf16-split GEMMs take M, N, K >= 4 (lbwn_gemm_launch), and the backward's epilogue options
+  // (column partials, dZ in chain order) exist in that form only: refuse here, not at the first
+  // backward after a whole forward
+  LBWN_REQUIRE((long)B * T >= 4, "plan: batch_sz * slice_sz >= 4 positions required (got %d x %d)", B, T);
   LBWN_REQUIRE(a->n_gc_embed >= 0 && (a->n_gc_embed == 0 || a->n_gc_category >= 1),
                "plan: GC needs n_gc_category >= 1");
   LBWN_REQUIRE(a->n_gc_embed <= 32, "plan: n_gc_embed > 32 not supported");

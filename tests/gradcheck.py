@@ -146,6 +146,59 @@ NO_BIAS_CASES = {
 }
 
 
+def arch3_arch():
+    import os
+    from lbwn.arch import load_arch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    return load_arch(os.path.join(root, 'par', 'arch3.json'))
+
+
+def _sa(**kw):
+    return lambda: small_arch(**kw)
+
+
+def _ca(C, **kw):
+    return lambda: cond_arch(1, 1, C, **kw)
+
+
+def edge_invalid(T):
+    """Masked head positions of an edge case: 37 as elsewhere, 1 where the slice is not longer than
+    that, 0 at T < 4 so that n_valid >= 1."""
+    return 37 if T > 37 else 1 if T >= 4 else 0
+
+
+def _edge(prefix, mk, shapes, cond=False, seed=0):
+    return {'%s_%dx%d' % (prefix, B, T): (mk, B, T, edge_invalid(T), seed, cond) for B, T in shapes}
+
+
+# The ends of the depth and slice ranges lbwn_plan_create accepts (n_blocks >= 1, n_block_layers in
+# 1..16, slice_sz >= 2, at least 4 positions) that tests/test_gpu_edge_shapes.py holds against
+# float64, in the shape of NO_BIAS_CASES: (arch, B, T, masked head positions, parameter seed, conditioned).
+# tests/test_edge_shapes.py counts each one's relu ties on the CPU; a case that passes the cap takes
+# another seed here, never a wider cap.  L1*: one layer (the first is the last), H = 1.  L2*: two
+# layers (the chains' min(l + 2, L - 1) prefetches).  tiny*: M = 4 .. 360, T below 4 / 16 / 32.
+# deep*: n_block_layers 12 and 16 (d and H up to 32768).
+EDGE_CASES = {}
+EDGE_CASES.update(_edge('L1', _sa(nb=1, nbl=1), [(2, 256)]))
+# seed 1, not 0: seed 0 has 4 of 8256 elements of S within the forward bar of zero, and the cap is 4.1
+EDGE_CASES.update(_edge('L1', _sa(nb=1, nbl=1), [(1, 129)], seed=1))
+EDGE_CASES.update(_edge('L2_d1', _sa(nb=2, nbl=1), [(2, 256)]))
+EDGE_CASES.update(_edge('L2', _sa(nb=1, nbl=2), [(3, 200)]))
+EDGE_CASES.update(_edge('L1_c16', _sa(nb=1, nbl=1, Cr=16, Cd=16), [(2, 256)]))
+EDGE_CASES.update(_edge('L1_cond32', _ca(32, n_blocks=1, n_block_layers=1), [(2, 136)], cond=True))
+EDGE_CASES.update(_edge('L2_cond32', _ca(32, n_blocks=2, n_block_layers=1), [(2, 136)], cond=True))
+EDGE_CASES.update(_edge('L1_cond16', _ca(16, n_blocks=1, n_block_layers=1), [(2, 136)], cond=True))
+# (2, 2) and (2, 3), not (1, 2) and (1, 3): lbwn_plan_create refuses fewer than 4 positions (include/lbwn.h)
+EDGE_CASES.update(_edge('tiny', _sa(), [(2, 2), (2, 3), (3, 5), (2, 17), (7, 31), (40, 9)]))
+EDGE_CASES.update(_edge('tiny_arch3', arch3_arch, [(2, 8)]))
+EDGE_CASES.update(_edge('tiny_arch2w', _sa(Cr=3, Cd=4, Cs=8, Cp=6), [(3, 5)]))
+EDGE_CASES.update(_edge('tiny_cond32', _ca(32), [(2, 8), (5, 16)], cond=True))
+EDGE_CASES.update(_edge('tiny_cond16', _ca(16), [(3, 8)], cond=True))
+EDGE_CASES.update(_edge('deep12', _sa(nb=1, nbl=12), [(2, 2200)]))
+EDGE_CASES.update(_edge('deep12_c16', _sa(nb=1, nbl=12, Cr=16, Cd=16), [(2, 2200)]))
+EDGE_CASES.update(_edge('deep16', _sa(nb=1, nbl=16), [(2, 300)]))
+
+
 def rand_batch(arch, B, T, seed=0, invalid=37):
     rng = np.random.default_rng(seed)
     q = rng.integers(0, arch['n_quant'], size=(B, T)).astype(np.int32)
@@ -170,6 +223,26 @@ def cond_batch(arch, B, T, invalid=37):
     mel = None
     if arch['n_lc_out'] > 0:
         hop = int(np.prod(arch['lc_upsample']))
+        mel = rng.standard_normal((B, T // hop, arch['n_lc_in'])).astype(np.float32)
+    return q, ids, mel
+
+
+def edge_cond_batch(arch, B, T, invalid=1):
+    """cond_batch for slices of any length >= 2 (cond_batch needs T >= 43 for its three cuts):
+    rand_batch with, for GC archs, one voice change per stream at a random position in [1, T)
+    (masked positions stay 0, ids[:, 0] = 0) and, for LC archs, a mel input of T / hop frames."""
+    q, ids = rand_batch(arch, B, T, invalid=max(invalid, 1))
+    rng = np.random.default_rng(3)
+    if arch['n_gc_embed'] > 0:
+        for b in range(B):
+            cut = int(rng.integers(1, T))
+            v = rng.choice(np.arange(1, arch['n_gc_category'] + 1), 2, replace=False)
+            ids[b] = np.where(ids[b] != 0, np.repeat(v, [cut, T - cut]), 0)
+    ids[:, 0] = 0
+    mel = None
+    if arch['n_lc_out'] > 0:
+        hop = int(np.prod(arch['lc_upsample']))
+        assert T % hop == 0
         mel = rng.standard_normal((B, T // hop, arch['n_lc_in'])).astype(np.float32)
     return q, ids, mel
 

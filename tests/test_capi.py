@@ -88,6 +88,31 @@ def test_plan_rejects_bad_arch_without_gpu():
     lib.lbwn_plan_destroy(h)
 
 
+def test_plan_rejects_fewer_than_four_positions_without_gpu():
+    """include/lbwn.h: batch_sz * slice_sz >= 4 (the bf16-split GEMMs take no fewer than 4 rows, and
+    the backward's epilogue options exist in that form only); slice_sz >= 2; the ends of the depth
+    range are accepted."""
+    import ctypes
+    from lbwn import _lib
+    lib = _lib.load()
+    a = _lib.Arch()
+    a.n_blocks, a.n_block_layers, a.n_quant, a.n_res, a.n_dil, a.n_skip, a.n_post = 2, 4, 256, 32, 32, 64, 32
+    h = ctypes.c_void_p()
+    for B, T in ((1, 2), (1, 3)):
+        assert lib.lbwn_plan_create(ctypes.byref(a), B, T, ctypes.byref(h)) == 22, (B, T)
+        assert b'batch_sz * slice_sz >= 4' in lib.lbwn_last_error()
+    assert lib.lbwn_plan_create(ctypes.byref(a), 4, 1, ctypes.byref(h)) == 22
+    assert b'slice_sz >= 2' in lib.lbwn_last_error()
+    for B, T in ((2, 2), (1, 4), (2, 3)):
+        assert lib.lbwn_plan_create(ctypes.byref(a), B, T, ctypes.byref(h)) == 0, (B, T)
+        lib.lbwn_plan_destroy(h)
+    for nb, nbl, want in ((1, 1, 0), (1, 16, 0), (1, 17, 22), (0, 4, 22)):
+        a.n_blocks, a.n_block_layers = nb, nbl
+        assert lib.lbwn_plan_create(ctypes.byref(a), 2, 300, ctypes.byref(h)) == want, (nb, nbl)
+        if want == 0:
+            lib.lbwn_plan_destroy(h)
+
+
 def test_torch_ops_registered_device_only():
     """lbwn::dilconv_gate / lbwn::dilconv_gate_bwd are torch.library ops with autograd; they have
     no CPU kernel (the oracle is never a fallback), so CPU tensors fail loudly."""

@@ -427,7 +427,7 @@ def all_grads_finite(net):
 
 def check_plan(arch, B, T, invalid=37, title='', poison_grads=False, seed=0):
     """seed: of the parameters (a case whose relu ties pass the cap takes another).  poison_grads: fill net.grad_flat with NaN before the backward and assert that every gradient
-    is finite after it, before the comparisons."""
+    is finite after it, before the comparisons.  Returns the net after its backward."""
     net = make_net(arch, B, seed=seed)
     q, ids = rand_batch(arch, B, T, invalid=invalid)
     P, S, lg, cache, new_save, st, dlog = _run_oracle(arch, net, q, ids)
@@ -488,6 +488,7 @@ def check_plan(arch, B, T, invalid=37, title='', poison_grads=False, seed=0):
     if inter:
         check_bwd_intermediates(net, arch, B, T, cache, dlog, st['n_valid'], worst)
     worst.report('%s (relu ties adopted: %d of S, %d of h1)' % ((title,) + adopted))
+    return net
 
 
 @pytest.mark.parametrize('B,T,nbl', [(4, 9000, 10), (2, 300, 3)])
@@ -539,13 +540,14 @@ def test_plan_conditioning_ragged(chain_tile):
     check_conditioning(1, 1, 32, 3, 136, chain_tile)
 
 
-def check_conditioning(gc, lc, C, B, T, chain_tile, arch=None, seed=0, poison_grads=False):
+def check_conditioning(gc, lc, C, B, T, chain_tile, arch=None, seed=0, poison_grads=False, batch=cond_batch):
     """arch: another conditioned arch than cond_arch(gc, lc, C) (tests/test_gpu_cond_plan.py); seed:
-    of the parameters; poison_grads: as check_plan.  Returns the net after its backward (its plan_info
-    is then complete)."""
+    of the parameters; poison_grads: as check_plan; batch: another (arch, B, T) -> (q, ids, mel) than
+    cond_batch (slices too short for its cuts).  Returns the net after its backward (its plan_info is
+    then complete)."""
     arch = arch or cond_arch(gc, lc, C)
     net = make_net(arch, B, seed=seed)
-    q, ids, mel = cond_batch(arch, B, T)
+    q, ids, mel = batch(arch, B, T)
     P, S = oracle_params(net)
     lg, cache, new_save = R.forward(arch, P, q, ids, S, mel=mel)
     st, dlog = R.loss_fcn(arch, P, lg, q, ids, 0.0)

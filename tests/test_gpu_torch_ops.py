@@ -22,7 +22,9 @@ def reference(xh, ws, wg, bs, bg, wr, br, d, H):
 
 
 @pytest.mark.parametrize('d,T,Cr,Cd', [(1, 300, 32, 32), (16, 257, 32, 32), (128, 300, 32, 32), (256, 600, 32, 32),
-                                       (4, 200, 24, 16)])
+                                       (4, 200, 24, 16),
+                                       # slices of 1, 3 and 31 positions (T < d, less than one 32-row block)
+                                       (1, 1, 32, 32), (4, 3, 32, 32), (256, 31, 32, 32), (4, 3, 24, 16)])
 def test_dilconv_gate_fwd_bwd_vs_torch_fp64(d, T, Cr, Cd):
     H, B = 256, 2
     g = torch.Generator().manual_seed(d * 7 + T)

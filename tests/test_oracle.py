@@ -96,13 +96,13 @@ def test_readme_influence_kat():
 
 # ---- training forward: staged == unstaged, finite differences --------------------------
 
-def _setup(arch, B=2, T=24, seed=0, bias_scale=0.1):
+def _setup(arch, B=2, T=24, seed=0, bias_scale=0.1, invalid=5):
     rng = np.random.default_rng(seed)
     P = R.init_params(arch, rng, bias_scale=bias_scale)
     save = R.init_save(arch, B, rng)
     q = rng.integers(0, arch['n_quant'], size=(B, T))
     ids = rng.integers(1, max(arch['n_gc_category'], 1) + 1, size=(B, T))
-    ids[:, :5] = 0
+    ids[:, :invalid] = 0
     mel = None
     if arch['n_lc_out']:
         hop = int(np.prod(arch['lc_upsample']))
@@ -124,10 +124,22 @@ def test_staged_equals_unstaged(gc, lc):
         np.testing.assert_allclose(sv2[k], sv[k], rtol=0, atol=0)
 
 
-@pytest.mark.parametrize('gc,lc,ub', [(0, 0, True), (3, 1, True), (0, 0, False), (3, 1, False)])
-def test_backward_finite_difference(gc, lc, ub):
-    arch = arch_tiny(gc, lc, ub=ub)
-    P, save, q, ids, mel = _setup(arch, T=16)
+def _fd(gc, lc, ub, nb=2, nbl=3, B=2, T=16, id=None):
+    return pytest.param(gc, lc, ub, nb, nbl, B, T, id=id or '%d-%d-%s' % (gc, lc, ub))
+
+
+@pytest.mark.parametrize('gc,lc,ub,nb,nbl,B,T', [
+    _fd(0, 0, True), _fd(3, 1, True), _fd(0, 0, False), _fd(3, 1, False),
+    # the ends of the depth and slice ranges tests/test_gpu_edge_shapes.py leans on the oracle at: one
+    # layer, two layers of dilation 1, slices of 2 and 3 positions, and n_block_layers = 12 with
+    # every dilation >= 64 past the slice
+    _fd(0, 0, True, nb=1, nbl=1, id='L1'), _fd(3, 1, True, nb=1, nbl=1, id='L1-gc-lc'),
+    _fd(0, 0, True, nb=2, nbl=1, id='L2-d1'), _fd(3, 1, True, nb=2, nbl=1, id='L2-d1-gc-lc'),
+    _fd(0, 0, True, B=2, T=2, id='2x2'), _fd(0, 0, True, B=1, T=3, id='1x3'),
+    _fd(0, 0, True, nb=1, nbl=12, T=40, id='nbl12-T40')])
+def test_backward_finite_difference(gc, lc, ub, nb, nbl, B, T):
+    arch = arch_tiny(gc, lc, nbl=nbl, nb=nb, ub=ub)
+    P, save, q, ids, mel = _setup(arch, B=B, T=T, invalid=5 if T > 5 else 0)
     l2f = 0.01
 
     def total(P_):
