@@ -381,6 +381,60 @@ int lbwn_gen_state_save(const lbwn_gen_plan* plan, const void* workspace, void* 
 int lbwn_gen_state_load(lbwn_gen_plan* plan, void* workspace, const void* state, int state_streams,
                         const int* src_stream, void* stream);
 
+/* ---- log-mel front end: wav to the LC conditioning, one launch (added after ABI 5 was declared, same
+ * ABI: symbols added, none altered) ----
+ * The reference made its mels offline with librosa (data.py:143 keeps len(wav) == len(mel)·hop); this is
+ * that transform on the device.  For a mono signal x[0..n) per stream:
+ *   frames  F = n / hop (a tail shorter than a hop is dropped); frame t is centred at sample t·hop: its
+ *           sample k < n_fft is x~[t·hop + k - n_fft/2] with reflect padding that does not repeat the edge
+ *           (x~[i] = x[-i] for i < 0, x[2(n-1) - i] for i >= n).  n > n_fft/2 (one reflection) and F >= 1.
+ *   window  periodic Hann of win_length, w[j] = 0.5 - 0.5·cos(2πj/win_length), zero-padded centrally
+ *           (left pad (n_fft - win_length)/2) to n_fft.
+ *   P[k]    = |Σ_j w[j]·frame[j]·e^(-2πi·jk/n_fft)|^power, k = 0..n_fft/2.
+ *   M[j]    = Σ_k P[k]·fb[k][j]: triangles over n_mels + 2 points equally spaced on the mel scale between
+ *           fmin and fmax (Slaney: linear below 1 kHz at 200/3 Hz per mel, log above with step ln(6.4)/27;
+ *           htk = 1: 2595·log10(1 + f/700)); weight of bin frequency f = k·sample_rate/n_fft in band j:
+ *           max(0, min((f - p_j)/(p_j+1 - p_j), (p_j+2 - f)/(p_j+2 - p_j+1))), times 2/(p_j+2 - p_j) with
+ *           norm = 1.  Built on the host in double, rounded once to f32.
+ *   out     ln(max(M, log_floor)) with log_floor > 0, the linear M with log_floor = 0; fp32 [B][F][n_mels].
+ * lbwn_mel_plan_create is host-only (no GPU needed).  struct_size = sizeof(lbwn_mel_cfg), else EINVAL.
+ * EINVAL naming the argument: n_fft not a multiple of 32 in [64, 2048]; hop not a multiple of 4 in
+ * [4, n_fft]; win_length outside [2, n_fft]; n_mels not a multiple of 4 in [4, 128]; not 0 <= fmin < fmax
+ * <= sample_rate/2; power not 1 or 2; log_floor negative or not finite; a filterbank with an empty band
+ * (an all-zero column); a frame tile (64 frames, else 32: (rows-1)·hop + n_fft samples) beyond the device's
+ * 160 KiB of LDS.
+ * lbwn_mel_frames: F for a signal of n_samples, 0 when the length is refused.
+ * lbwn_mel_workspace_bytes: the tables (the windowed DFT basis and the filterbank); independent of the
+ * signal length.  The workspace is caller-owned device memory, 256-byte aligned.
+ * lbwn_mel_filterbank: the [n_fft/2+1][n_mels] f32 filterbank to host memory; touches no device.
+ * lbwn_mel_init: fills the tables (one launch and one copy from plan-owned host memory) and raises the
+ * forward kernel's dynamic-LDS limit on the current device, so that lbwn_mel_forward is the launch alone;
+ * once per workspace (hence at least once per device and process before the first forward there); the
+ * plan must outlive the copy; not graph-capturable.  The tables depend on the configuration alone: two
+ * workspaces hold the same bits.
+ * lbwn_mel_forward: stream b < batch is read at wav + b·ld_wav (n_samples floats) and its F rows are
+ * written densely [F][n_mels] at out + b·ld_out_stream; nothing else is read or written.  One launch,
+ * stream-ordered, no allocation or synchronisation, graph-capturable, deterministic (no float atomics;
+ * a stream's rows do not depend on the batch).  EINVAL before any launch: a null argument, wav or out not
+ * 16-byte aligned, ld_wav not a multiple of 4 or (batch > 1) < n_samples, ld_out_stream < F·n_mels
+ * (batch > 1), batch outside [1, 65535], n_samples that lbwn_mel_frames refuses. */
+typedef struct lbwn_mel_cfg {
+  size_t struct_size;
+  int sample_rate, n_fft, win_length, hop, n_mels;
+  float fmin, fmax;
+  int power, htk, norm;
+  float log_floor;
+} lbwn_mel_cfg;
+typedef struct lbwn_mel_plan lbwn_mel_plan;
+int lbwn_mel_plan_create(const lbwn_mel_cfg* cfg, lbwn_mel_plan** out);
+void lbwn_mel_plan_destroy(lbwn_mel_plan* plan);
+int64_t lbwn_mel_frames(const lbwn_mel_plan* plan, int64_t n_samples);
+size_t lbwn_mel_workspace_bytes(const lbwn_mel_plan* plan);
+int lbwn_mel_filterbank(const lbwn_mel_plan* plan, float* host_out);
+int lbwn_mel_init(const lbwn_mel_plan* plan, void* workspace, void* stream);
+int lbwn_mel_forward(const lbwn_mel_plan* plan, const void* workspace, const float* wav, int64_t ld_wav, int batch,
+                     int64_t n_samples, float* out, int64_t ld_out_stream, void* stream);
+
 /* ---- fine-grained kernels (parity tests, custom drivers) ------------------------------ */
 /* ops.mu_encode_np (ops.py:23-28, tf32=0, float64 math) / ops.mu_encode (ops.py:4-9, tf32=1) */
 int lbwn_mulaw_encode(const float* x, int* q, int64_t n, int n_quanta, int tf32, void* stream);

@@ -310,3 +310,21 @@ int lbwn_lc_up_bwd_launch(int nup, const int* s, int Li, int Lo, int frames, con
                           float* const* act, const float* dlc, float* dpart, float* const* dF, hipStream_t st,
                           hipStream_t st_sum = nullptr, hipEvent_t ev = nullptr, int dlc_parts = 1,
                           long dlc_stride = 0);
+
+// Log-mel front end (mel.hip).  The tables live in the caller's workspace:
+// basis [ncb][n_fft/4][2 (cos | sin)][32 bins][4 samples] f32 (windowed, zero past bin n_fft/2), then
+// the filterbank [ncb·32][nt·32] f32 (zero-padded), 256-byte aligned.
+struct lbwn_mel_dims {
+  int n_fft, win, hop, n_mels, power;
+  int nbins, ncb, nt;     // n_fft/2+1 bins in ncb 32-bin column blocks; nt 32-band tiles
+  int cb_lo, cb_hi;       // the column blocks that hold a bin with a nonzero filterbank row: [cb_lo, cb_hi)
+  int rows;               // frames per block: 64 or 32
+  float log_floor;
+};
+size_t lbwn_mel_basis_floats(const lbwn_mel_dims& d);
+size_t lbwn_mel_lds_bytes(const lbwn_mel_dims& d, int rows);
+int lbwn_mel_basis_launch(const lbwn_mel_dims& d, float* basis, hipStream_t st);
+// once per device before the first lbwn_mel_fwd_launch of these dims: the kernel's dynamic-LDS limit
+int lbwn_mel_fwd_prepare(const lbwn_mel_dims& d);
+int lbwn_mel_fwd_launch(const lbwn_mel_dims& d, const float* basis, const float* fb, const float* wav, long ld_wav,
+                        int batch, long n, long frames, float* out, long ld_out, hipStream_t st);

@@ -6,7 +6,9 @@ while_loop becomes WaveNetGen's device-resident generation (hipGraph-replayed ch
 librosa (absent here) is replaced by scipy.io.wavfile for reading the teacher wav and
 writing 'gen.i<k>.wav' (float32).  The reference hard-codes gc_ids = [5, 6]
 (generate.py:94); --gc-ids overrides, and the list is cycled over the batch.  Archs with local
-conditioning (the reference's generator has none) take their mel from --mel-npy.
+conditioning (the reference's generator has none) take their mel from --mel-npy, or compute it on the
+device from a wav with --mel-from-wav (lbwn.mel.MelSpectrogram: n_fft 1024, Slaney, power 2, ln floor 1e-5
+unless --mel-config names the mel_config.json that make_mels.py wrote).
 --teacher-prefill (build extension, off by default) runs the teacher's steps as one parallel prefill;
 the written wav then starts with the µ-law-quantised teacher instead of the draws the model made, and
 ignored, during those steps.  With --mel-npy the prefilled steps are conditioned on the mel like the
@@ -67,6 +69,13 @@ def get_args(argv=None):
                         '(shared by the batch) or [batch, frames, n_lc_in].  Upsampled mel row i-1 conditions '
                         'step i, counted from the start of the teacher (step 0 uses row 0), so it must hold '
                         'at least (steps - 1) / hop frames for the gen_seconds + teacher seconds requested')
+    p.add_argument('--mel-from-wav', type=str, default=None, metavar='PATH',
+                   help='(build extension) local conditioning for LC archs computed on the device from this wav '
+                        '(read like --teacher-wav; --teacher-start / --teacher-duration apply when PATH is also '
+                        'the --teacher-wav); used as the shared [frames, n_lc_in] mel; not with --mel-npy')
+    p.add_argument('--mel-config', type=str, default=None, metavar='JSON',
+                   help='(build extension) with --mel-from-wav: the mel_config.json make_mels.py wrote; its hop '
+                        'and n_mels must equal the arch\'s')
     p.add_argument('--temperature', type=float, default=1.0,
                    help='(build extension) softmax temperature of the draw, finite and > 0 (1 = off)')
     p.add_argument('--top-k', type=int, default=0,
@@ -135,8 +144,38 @@ def main(argv=None):
     if args.score_npy is not None and not args.score_teacher:
         print('--score-npy needs --score-teacher', file=stderr)
         sys.exit(1)
+    if args.mel_from_wav is not None and args.mel_npy is not None:
+        print('--mel-from-wav and --mel-npy both give the mel: pass one of them', file=stderr)
+        sys.exit(1)
+    if args.mel_config is not None and args.mel_from_wav is None:
+        print('--mel-config needs --mel-from-wav', file=stderr)
+        sys.exit(1)
     with open(args.arch_file) as fp:
         arch = normalize_arch(json.load(fp))
+    mel_cfg = None
+    if args.mel_from_wav is not None:
+        if arch['n_lc_out'] == 0:
+            print('--mel-from-wav: ARCH_FILE has no local conditioning', file=stderr)
+            sys.exit(1)
+        mel_cfg = dict(sample_rate=args.sample_rate, hop=mel_hop_sz(arch), n_mels=arch['n_lc_in'])
+        if args.mel_config is not None:
+            from lbwn.mel import check_config
+            try:
+                with open(args.mel_config) as fp:
+                    mel_cfg = json.load(fp)
+                check_config(mel_cfg)
+            except (OSError, ValueError) as e:           # unreadable, not JSON, or keys missing / unknown
+                print('--mel-config {}: {}'.format(args.mel_config, e), file=stderr)
+                sys.exit(1)
+            if mel_cfg['hop'] != mel_hop_sz(arch) or mel_cfg['n_mels'] != arch['n_lc_in']:
+                print('--mel-config {}: hop {} and n_mels {} do not match the arch (hop {}, n_lc_in {})'.format(
+                    args.mel_config, mel_cfg['hop'], mel_cfg['n_mels'], mel_hop_sz(arch), arch['n_lc_in']),
+                    file=stderr)
+                sys.exit(1)
+            if mel_cfg['sample_rate'] != args.sample_rate:
+                print('--mel-config {}: sample_rate {} is not --sample-rate {}'.format(
+                    args.mel_config, mel_cfg['sample_rate'], args.sample_rate), file=stderr)
+                sys.exit(1)
     if not os.access(ckpt_file(args.ckpt), os.R_OK):                   # generate.py:43-47
         print("Couldn't find checkpoint file {}".format(ckpt_file(args.ckpt)), file=stderr)
         sys.exit(1)
@@ -149,13 +188,28 @@ def main(argv=None):
     gen_sz = int((args.gen_seconds + teacher_seconds) * args.sample_rate)
     mel = None
     if arch['n_lc_out'] > 0:
-        if args.mel_npy is None:
+        if args.mel_npy is None and args.mel_from_wav is None:
             print('ARCH_FILE has local conditioning: --mel-npy is required', file=stderr)
             sys.exit(1)
-        if not os.access(args.mel_npy, os.R_OK):
-            print("Couldn't find mel file {}".format(args.mel_npy), file=stderr)
-            sys.exit(1)
-        mel = np.load(args.mel_npy)
+        if args.mel_from_wav is not None:
+            if not os.access(args.mel_from_wav, os.R_OK):
+                print("Couldn't find wav file {}".format(args.mel_from_wav), file=stderr)
+                sys.exit(1)
+            from lbwn.mel import MelSpectrogram
+            same = args.mel_from_wav == args.teacher_wav
+            mel_wav = load_teacher(args.mel_from_wav, args.sample_rate, args.teacher_start if same else None,
+                                   args.teacher_duration if same else None)
+            try:
+                mel = MelSpectrogram.from_config(mel_cfg)(mel_wav).cpu().numpy()
+            except (RuntimeError, ValueError, TypeError) as e:     # a setting the library refuses
+                                                                   # (LbwnError), or of the wrong type
+                print('--mel-from-wav {}: {}'.format(args.mel_from_wav, e), file=stderr)
+                sys.exit(1)
+        else:
+            if not os.access(args.mel_npy, os.R_OK):
+                print("Couldn't find mel file {}".format(args.mel_npy), file=stderr)
+                sys.exit(1)
+            mel = np.load(args.mel_npy)
         hop = mel_hop_sz(arch)
         if mel.ndim not in (2, 3) or gen_sz > mel.shape[-2] * hop + 1:
             print('mel {} is too short: {} steps ({} s generated + {} s teacher) need {} frames of hop {}'.format(

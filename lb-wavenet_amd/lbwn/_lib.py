@@ -72,7 +72,25 @@ class AdamExArgs(ctypes.Structure):
         self.struct_size = ctypes.sizeof(AdamExArgs)
 
 
+class MelCfg(ctypes.Structure):
+    """lbwn_mel_cfg (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('sample_rate', c_int), ('n_fft', c_int), ('win_length', c_int),
+                ('hop', c_int), ('n_mels', c_int), ('fmin', c_float), ('fmax', c_float),
+                ('power', c_int), ('htk', c_int), ('norm', c_int), ('log_floor', c_float)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(MelCfg)
+
+
 _SIGS = {
+    'lbwn_mel_plan_create': (c_int, [ctypes.POINTER(MelCfg), ctypes.POINTER(c_void_p)]),
+    'lbwn_mel_plan_destroy': (None, [c_void_p]),
+    'lbwn_mel_frames': (c_int64, [c_void_p, c_int64]),
+    'lbwn_mel_workspace_bytes': (c_size_t, [c_void_p]),
+    'lbwn_mel_filterbank': (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    'lbwn_mel_init': (c_int, [c_void_p, c_fp, c_void_p]),
+    'lbwn_mel_forward': (c_int, [c_void_p, c_fp, c_fp, c_int64, c_int, c_int64, c_fp, c_int64, c_void_p]),
     'lbwn_last_error': (ctypes.c_char_p, []),
     'lbwn_abi_version': (c_int, []),
     'lbwn_recep_field_sz': (c_int, [ctypes.POINTER(Arch)]),
