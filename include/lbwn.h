@@ -123,6 +123,57 @@ int lbwn_train_forward(lbwn_plan* plan, const lbwn_params* params, void* workspa
 int lbwn_train_backward(lbwn_plan* plan, const lbwn_params* params, const lbwn_params* grads, void* workspace,
                         const int* wav_q, const int* ids, const float* mel, void* stream);
 
+/* Held-out evaluation of one slice (added after ABI 5 was declared, same ABI: two symbols added, none
+ * altered).  Runs lbwn_train_forward's forward up to the raw logits [B·T][n_quant] -- the
+ * same launches and the same bits for the same inputs, weights and save: conditioning, D-sep prepend and
+ * save, head padding -- then scores the logits without writing a gradient.  params may be any buffer of
+ * the layout (the optimizer's EMA shadow, another checkpoint).
+ * Scoring (tmodel.py:228-249): position (b, t), t < T-1, has the target c = wav_q[b][t+1] and is scored
+ * iff ids[b][t+1] != 0.  Its value is the training head's xent in nats, (max + logf(Σ exp(l - max))) - l[c],
+ * and its argmax the first code holding the maximum.  A target outside [0, n_quant) is the caller's error:
+ * nothing is read for it and the row's value is its log-sum-exp.
+ *   acc     device double[4], required, ADDED to (zero it once per evaluation): [0] Σ value, [1] scored
+ *            positions, [2] Σ |argmax - c|, [3] positions with argmax == c.
+ *   nll      nullable device fp32 [B][ld_nll], ld_nll >= T: the value, or 0 where not scored and at
+ *            t = T-1; columns past T are not touched.
+ *   by_voice nullable device double [n_bins][2], ADDED to: [v][0] Σ value, [v][1] count over the scored
+ *            positions with v = ids[b][t+1]; ids outside [0, n_bins) are counted in bin 0, which no
+ *            scored position otherwise uses.
+ *   status   nullable device word: the plan's status word of this call is ORed into it.
+ *   save     the evaluation's OWN D-sep state (lbwn_train_forward's layout), read and advanced in place as
+ *            in training, so consecutive slices of one deal chain.
+ *   scratch  caller-owned, 16-byte aligned, lbwn_train_eval_scratch_bytes(plan, n_bins) bytes (n_bins = 0
+ *            without by_voice; 0 for a NULL plan): head partials double [blocks][4] | voice partials double
+ *            [ceil(B·T/256)][n_bins][2] | row values fp32 [B·T], each part rounded up to 256 bytes.  The
+ *            plan's workspace size is what it was without this call.
+ * All sums are formed in double in an order the shapes alone fix (one wave per row, per-block partials,
+ * a fixed-order fold; per voice the positions in order inside 256-position chunks, then the chunks in
+ * order); no floating-point atomics: two calls on the same inputs add the same bits.
+ * Afterwards "logits" holds the raw logits and the plan has no training forward: a lbwn_train_backward
+ * that follows is refused (EINVAL); the next lbwn_train_forward works as ever.  n_quant is any multiple of
+ * 4 (the 1024 bound is the backward's).  Stream-ordered, no host synchronisation, no allocation.
+ * EINVAL before any launch and before the device is touched, naming the argument: a null plan, params,
+ * workspace, args, wav_q, ids, save, acc or scratch; struct_size != sizeof(lbwn_eval_args); mel NULL on an
+ * LC arch; ld_nll < T with nll; n_bins < 1 with by_voice; acc or by_voice not 8-byte aligned; scratch
+ * not 16-byte aligned. */
+typedef struct lbwn_eval_args {
+  size_t struct_size;
+  const int* wav_q;
+  const int* ids;
+  const float* mel;
+  float* save;
+  double* acc;
+  float* nll;
+  int64_t ld_nll;
+  double* by_voice;
+  int n_bins;
+  uint32_t* status;
+  void* scratch;
+} lbwn_eval_args;
+size_t lbwn_train_eval_scratch_bytes(const lbwn_plan* plan, int n_bins);
+int lbwn_train_eval(lbwn_plan* plan, const lbwn_params* params, void* workspace, const lbwn_eval_args* a,
+                    void* stream);
+
 /* tf.train.AdamOptimizer.apply_gradients (train.py:178, :186), TF1 semantics, over the
  * flat buffers [0, n_total); elements [0, n_weights) are non-BIAS trainables and get the
  * l2 term (tmodel.py:250-261): g = raw·inv_n + l2_factor·θ with inv_n = 1/stats[1]

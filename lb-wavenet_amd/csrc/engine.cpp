@@ -852,13 +852,13 @@ int lc_upsample_bwd(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, vo
 
 }  // namespace
 
-int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* wav_q, const int* ids,
-                       const float* mel, float* save, float* stats, void* stream) {
-  LBWN_REQUIRE(p && P && ws && wav_q && ids && save && stats, "train_forward: null argument");
-  hipStream_t st = (hipStream_t)stream;
+// The forward of one slice up to the raw logits [M][n_quant] in the workspace: conditioning, D-sep
+// prepend / save, the layer stack and the three head GEMMs.  lbwn_train_forward follows it with the
+// training head, lbwn_train_eval with the evaluation head: the same launches and bits up to here.
+static int forward_to_logits(lbwn_plan* p, const lbwn_params* P, void* ws, const int* wav_q, const int* ids,
+                             const float* mel, float* save, hipStream_t st) {
   int e;
   if ((e = ensure_device(p))) return e;
-  LBWN_REQUIRE(p->Lo == 0 || mel, "train_forward: LC arch needs the mel input");
   lbwn_params Ppad;
   if ((e = head_pad_params(p, P, ws, Ppad, true, st))) return e;
   P = &Ppad;
@@ -1025,6 +1025,19 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
   Probe(p, st, "post2_fwd");
   if ((e = lbwn_gemm_launch(g, 1, 0, 1, nullptr, st))) return e;
   Probe::end(p, st, "post2_fwd");
+  return 0;
+}
+
+int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* wav_q, const int* ids,
+                       const float* mel, float* save, float* stats, void* stream) {
+  LBWN_REQUIRE(p && P && ws && wav_q && ids && save && stats, "train_forward: null argument");
+  LBWN_REQUIRE(p->Lo == 0 || mel, "train_forward: LC arch needs the mel input");
+  hipStream_t st = (hipStream_t)stream;
+  int e;
+  if ((e = forward_to_logits(p, P, ws, wav_q, ids, mel, save, st))) return e;
+  const int B = p->B, T = p->T;
+  const long M = p->M;
+  float* LOG = at<float>(ws, p->oLOG);
   // masked softmax-xent (+ unnormalised dlogits in place)  (tmodel.py:228-249)
   lbwn_head_args h;
   h.logits = LOG; h.q = wav_q; h.ids = ids; h.B = B; h.T = T; h.Q = p->Q;
@@ -1040,6 +1053,41 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
   return lbwn_stats_reduce_launch(h.partial, nb, stats, st);
 }
 
+// Held-out evaluation of one slice (include/lbwn.h): the forward above, then the evaluation head
+// over the raw logits.  Every argument check precedes the first device call.
+size_t lbwn_train_eval_scratch_bytes(const lbwn_plan* p, int n_bins) {
+  return p ? lbwn_eval_scratch_bytes(p->M, n_bins) : 0;
+}
+
+int lbwn_train_eval(lbwn_plan* p, const lbwn_params* P, void* ws, const lbwn_eval_args* a, void* stream) {
+  LBWN_REQUIRE(p, "train_eval: plan is null");
+  LBWN_REQUIRE(P, "train_eval: params is null");
+  LBWN_REQUIRE(ws, "train_eval: workspace is null");
+  LBWN_REQUIRE(a, "train_eval: args is null");
+  LBWN_REQUIRE(a->struct_size == sizeof(lbwn_eval_args), "train_eval: struct_size %zu != %zu (another ABI?)",
+               a->struct_size, sizeof(lbwn_eval_args));
+  LBWN_REQUIRE(a->wav_q, "train_eval: wav_q is null");
+  LBWN_REQUIRE(a->ids, "train_eval: ids is null");
+  LBWN_REQUIRE(a->save, "train_eval: save is null");
+  LBWN_REQUIRE(a->acc, "train_eval: acc is null");
+  LBWN_REQUIRE(a->scratch, "train_eval: scratch is null");
+  LBWN_REQUIRE(p->Lo == 0 || a->mel, "train_eval: mel is null on an LC arch");
+  LBWN_REQUIRE(!a->nll || a->ld_nll >= p->T, "train_eval: ld_nll %lld < slice_sz %d", (long long)a->ld_nll, p->T);
+  LBWN_REQUIRE(!a->by_voice || a->n_bins >= 1, "train_eval: n_bins must be >= 1 with by_voice (got %d)", a->n_bins);
+  LBWN_REQUIRE(!((uintptr_t)a->acc & 7), "train_eval: acc must be 8-byte aligned");
+  LBWN_REQUIRE(!((uintptr_t)a->by_voice & 7), "train_eval: by_voice must be 8-byte aligned");
+  LBWN_REQUIRE(!((uintptr_t)a->scratch & 15), "train_eval: scratch must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  int e;
+  if ((e = forward_to_logits(p, P, ws, a->wav_q, a->ids, a->mel, a->save, st))) return e;
+  // the workspace holds no gradient of this slice: a backward must follow a training forward
+  p->fwd_mode = -1;
+  p->head_colparts = 0;
+  return lbwn_eval_head_launch(at<float>(ws, p->oLOG), a->wav_q, a->ids, p->B, p->T, p->Q, a->nll, (long)a->ld_nll,
+                               a->acc, a->by_voice, a->by_voice ? a->n_bins : 0, at<unsigned>(ws, p->oSTATUS),
+                               a->status, a->scratch, st);
+}
+
 // Backward (tmodel.py:338-340, TF autodiff of the graph above): head/skip GEMMs, then the
 // residual stack in reverse (one persistent chain launch, or one launch per layer), then
 // one batched reduction of every layer's weight-gradient partials, then dPRE.
@@ -1052,7 +1100,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   if ((e = ensure_device(p))) return e;
   // the backward consumes the forward's layout choices (SG rows, the head's column partials, dZ in
   // chain order), which follow the GEMM arithmetic: a mode switch in between would mix two paths
-  LBWN_REQUIRE(p->fwd_mode >= 0, "train_backward: no forward on this plan");
+  LBWN_REQUIRE(p->fwd_mode >= 0, "train_backward: no training forward on this plan (lbwn_train_eval leaves none)");
   LBWN_REQUIRE(p->fwd_mode == lbwn_gemm_mode(),
                "train_backward: the GEMM mode changed since the forward (%d -> %d); run the forward again",
                p->fwd_mode, lbwn_gemm_mode());

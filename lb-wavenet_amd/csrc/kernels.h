@@ -241,6 +241,24 @@ int lbwn_head_nblocks(long M, bool colpart);
 int lbwn_head_launch(const lbwn_head_args& a, int* nblocks_out, hipStream_t st);
 int lbwn_stats_reduce_launch(const float* partial, int nparts, float* stats, hipStream_t st);
 
+// lbwn_train_eval's head (misc.hip): the xent of the training head with no gradient written, per-block
+// partials in double, then a fixed-order fold into acc / by_voice
+struct lbwn_eval_head_args {
+  const float* logits;      // [M][Q], read only
+  const int* q;             // [B][T] targets
+  const int* ids;           // [B][T]
+  int B, T, Q;
+  float* nll;               // nullable: [B][ld_nll], the value or 0 where not scored
+  long ld_nll;
+  float* rowv;              // nullable: [M], the same values for the per-voice pass
+  double* partial;          // [nblocks][4] (Σnll, count, Σ|argmax - c|, hits)
+};
+int lbwn_eval_nblocks(long M);
+size_t lbwn_eval_scratch_bytes(long M, int n_bins);
+int lbwn_eval_head_launch(const float* logits, const int* q, const int* ids, int B, int T, int Q, float* nll,
+                          long ld_nll, double* acc, double* by_voice, int n_bins, const unsigned* plan_status,
+                          unsigned* status, void* scratch, hipStream_t st);
+
 // several column sums in one launch pair; ws holds Σ_j lbwn_colsum_ws_floats(M, N[j]) floats
 int lbwn_colsum_multi_launch(int njobs, const float* const* X, const long* ldx, const int* N, float* const* out,
                              const int* accumulate, int M, float* ws, hipStream_t st);

@@ -366,6 +366,189 @@ __global__ void stats_reduce_kernel(const float* partial, int nparts, float* sta
   }
 }
 
+// ---- evaluation head (lbwn_train_eval) -----------------------------------------------------------
+// The training head's xent without its gradient: the logits are read and never written.  One wave
+// per row, the row in registers for QV > 0 (Q <= 64·QV, head_reg_kernel's lane order c = lane +
+// 64·j, so Σe, the first-max argmax and the value are that kernel's bits); QV = 0 walks a row of
+// any width three times.  The target's logit is picked by lane compare in both forms, so a code
+// outside [0, Q) reads nothing and picks 0 (the register form's padded lanes, Q <= c < 64·QV, are
+// excluded by the compare with Q): its value is the row's lse.  Each wave adds its rows' values in
+// double in row order; a block stores ((w0 + w1) + w2) + w3 of (Σnll, count, Σ|argmax - c|, hits).
+// The grid is lbwn_eval_nblocks(M), a function of M alone: the same partials in every run and on
+// every device.
+constexpr int EV_MAXBLK = 2048;
+LBWN_DEV double block_sum256(double s, double* sh);   // below, with the Adam norm pass
+constexpr int EV_CHUNK = 256;   // positions per block of eval_voice_kernel
+
+template <int QV>
+__global__ __launch_bounds__(256) void eval_head_kernel(lbwn_eval_head_args a) {
+  __shared__ double part[4][4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long M = (long)a.B * a.T;
+  const int Q = a.Q;
+  double s_nll = 0.0, s_cnt = 0.0, s_diff = 0.0, s_hit = 0.0;
+  const long stride = (long)gridDim.x * 4;
+  long m = (long)blockIdx.x * 4 + w;
+  constexpr int NV = QV > 0 ? QV : 1;
+  float vn[NV];
+  int tn = 0, idn = 0;
+  if (m < M) {   // the first row's logits and target; then one row ahead, as in head_reg_kernel
+    const long mq = min(m + 1, M - 1);
+    if (QV > 0) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) vn[j] = a.logits[m * Q + min(lane + 64 * j, Q - 1)];
+    }
+    tn = a.q[mq];
+    idn = a.ids[mq];
+  }
+  for (; m < M; m += stride) {
+    const float* row = a.logits + m * Q;
+    float v[NV];
+    if (QV > 0) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) v[j] = (lane + 64 * j < Q) ? vn[j] : -INFINITY;
+    }
+    const int tgt = tn;
+    const int vid = idn;
+    {
+      const long mc = min(m + stride, M - 1), mq = min(mc + 1, M - 1);
+      if (QV > 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) vn[j] = a.logits[mc * Q + min(lane + 64 * j, Q - 1)];
+      }
+      tn = a.q[mq];
+      idn = a.ids[mq];
+    }
+    const int b = (int)(m / a.T), t = (int)(m - (long)b * a.T);
+    const bool scored = t != a.T - 1 && vid != 0;   // tmodel.py:231-232
+    float nll = 0.f;
+    if (scored) {   // wave-uniform
+      float mx = -INFINITY, se = 0.f, pick = 0.f;
+      int am = 0x7fffffff;
+      if (QV > 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) mx = fmaxf(mx, v[j]);
+        mx = wave_max(mx);
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+          if (am == 0x7fffffff && v[j] == mx) am = lane + 64 * j;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          se += (lane + 64 * j < Q) ? expf(v[j] - mx) : 0.f;
+          if (lane + 64 * j == tgt && tgt < Q) pick = v[j];   // not a padded lane's -INF
+        }
+      } else {
+        for (int c = lane; c < Q; c += 64) mx = fmaxf(mx, row[c]);
+        mx = wave_max(mx);
+        for (int c = lane; c < Q; c += 64) {
+          const float x = row[c];
+          if (am == 0x7fffffff && x == mx) am = c;
+          se += expf(x - mx);
+          if (c == tgt) pick = x;
+        }
+      }
+      am = wave_min(am);
+      se = wave_sum(se);
+      pick = wave_sum(pick);   // the one lane holding the target's logit; the rest add 0
+      nll = (mx + logf(se)) - pick;
+      s_nll += (double)nll;
+      s_cnt += 1.0;
+      s_diff += (double)abs(tgt - am);
+      s_hit += am == tgt ? 1.0 : 0.0;
+    }
+    if (lane == 0) {
+      if (a.nll) a.nll[(long)b * a.ld_nll + t] = nll;
+      if (a.rowv) a.rowv[m] = nll;
+    }
+  }
+  if (lane == 0) {
+    part[w][0] = s_nll;
+    part[w][1] = s_cnt;
+    part[w][2] = s_diff;
+    part[w][3] = s_hit;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    a.partial[(long)blockIdx.x * 4 + k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+  }
+}
+
+// Per-voice partials: block c takes positions [256c, 256c + 256) into LDS as (bin, value) pairs
+// (bin -1: not scored), then thread v walks the 256 pairs in position order and adds those of bin
+// v in double: no atomics on values, an order fixed by the position.  Only the bins between the
+// chunk's smallest and largest one are walked (a chunk lies in one or two files, so mostly one
+// bin); the rest store zeros.  vpart is [nchunks][n_bins][2] (Σnll, count).
+__global__ __launch_bounds__(256) void eval_voice_kernel(const float* __restrict__ val, long ldv, const int* __restrict__ ids,
+                                                         int B, int T, int n_bins, double* __restrict__ vpart) {
+  __shared__ int sbin[EV_CHUNK];
+  __shared__ float sval[EV_CHUNK];
+  __shared__ int lo, hi;
+  if (threadIdx.x == 0) { lo = 0x7fffffff; hi = -1; }
+  __syncthreads();
+  const long M = (long)B * T, m = (long)blockIdx.x * EV_CHUNK + threadIdx.x;
+  int bin = -1;
+  float x = 0.f;
+  if (m < M) {
+    const int b = (int)(m / T), t = (int)(m - (long)b * T);
+    if (t != T - 1) {
+      const int id = ids[m + 1];
+      if (id != 0) {
+        bin = (unsigned)id < (unsigned)n_bins ? id : 0;
+        x = val[(long)b * ldv + t];
+      }
+    }
+  }
+  sbin[threadIdx.x] = bin;
+  sval[threadIdx.x] = x;
+  if (bin >= 0) {   // integer min / max: the result does not depend on the order
+    atomicMin(&lo, bin);
+    atomicMax(&hi, bin);
+  }
+  __syncthreads();
+  const int l0 = lo, h0 = hi;
+  double* out = vpart + (long)blockIdx.x * n_bins * 2;
+  for (int v = threadIdx.x; v < n_bins; v += 256) {
+    double s = 0.0, n = 0.0;
+    if (v >= l0 && v <= h0) {
+      for (int i = 0; i < EV_CHUNK; ++i)
+        if (sbin[i] == v) { s += (double)sval[i]; n += 1.0; }
+    }
+    out[2 * v] = s;
+    out[2 * v + 1] = n;
+  }
+}
+
+// Fold: block 0 adds the head's block partials into acc (thread t sums partials t, t + 256, ... in
+// order, then the fixed LDS tree) and ORs the plan's status word into the caller's; blocks 1.. take
+// one bin per thread and add the chunks' partials in chunk order into by_voice.
+__global__ __launch_bounds__(256) void eval_fold_kernel(const double* __restrict__ partial, int nparts, double* acc,
+                                                        const double* __restrict__ vpart, int nchunks, int n_bins,
+                                                        double* by_voice, const unsigned* plan_status,
+                                                        unsigned* status) {
+  __shared__ double sh[256];
+  if (blockIdx.x == 0) {
+    for (int k = 0; k < 4; ++k) {   // uniform
+      double s = 0.0;
+      for (int p = threadIdx.x; p < nparts; p += 256) s += partial[(long)p * 4 + k];
+      const double tot = block_sum256(s, sh);
+      if (threadIdx.x == 0) acc[k] += tot;
+      __syncthreads();
+    }
+    if (threadIdx.x == 0 && status) *status |= *plan_status;
+    return;
+  }
+  const int v = (blockIdx.x - 1) * 256 + threadIdx.x;
+  if (v >= n_bins) return;
+  double s = 0.0, n = 0.0;
+  for (int c = 0; c < nchunks; ++c) {
+    s += vpart[((long)c * n_bins + v) * 2];
+    n += vpart[((long)c * n_bins + v) * 2 + 1];
+  }
+  by_voice[2 * v] += s;
+  by_voice[2 * v + 1] += n;
+}
+
 // ---- column sums (bias gradients), deterministic two-pass ------------------------------------
 // pass 1: block = CS_ROWS rows × all N columns (float4 groups × row lanes); pass 2: 1024
 // threads per 64 columns sum the chunk partials.  N % 4 == 0, N <= 1024.
@@ -750,6 +933,51 @@ int lbwn_head_nblocks(long M, bool colpart) {
 
 int lbwn_stats_reduce_launch(const float* partial, int nparts, float* stats, hipStream_t st) {
   stats_reduce_kernel<<<1, 256, 0, st>>>(partial, nparts, stats);
+  LBWN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- lbwn_train_eval's head: row kernel, per-voice partials, fold ----
+int lbwn_eval_nblocks(long M) { return (int)std::min<long>((M + 3) / 4, EV_MAXBLK); }
+int lbwn_eval_nchunks(long M) { return (int)((M + EV_CHUNK - 1) / EV_CHUNK); }
+
+// scratch: head partials double [nblocks][4] | voice partials double [nchunks][n_bins][2] | row values
+// float [M] (the last two only with bins), each part rounded up to 256 bytes
+static size_t ev_up(size_t b) { return (b + 255) / 256 * 256; }
+size_t lbwn_eval_scratch_bytes(long M, int n_bins) {
+  size_t n = ev_up(sizeof(double) * 4 * (size_t)lbwn_eval_nblocks(M));
+  if (n_bins > 0)
+    n += ev_up(sizeof(double) * 2 * (size_t)lbwn_eval_nchunks(M) * (size_t)n_bins) + ev_up(sizeof(float) * (size_t)M);
+  return n;
+}
+
+int lbwn_eval_head_launch(const float* logits, const int* q, const int* ids, int B, int T, int Q, float* nll,
+                          long ld_nll, double* acc, double* by_voice, int n_bins, const unsigned* plan_status,
+                          unsigned* status, void* scratch, hipStream_t st) {
+  const long M = (long)B * T;
+  char* sc = static_cast<char*>(scratch);
+  lbwn_eval_head_args a;
+  a.logits = logits; a.q = q; a.ids = ids; a.B = B; a.T = T; a.Q = Q; a.nll = nll; a.ld_nll = ld_nll;
+  a.partial = reinterpret_cast<double*>(sc);
+  const int nb = lbwn_eval_nblocks(M), nch = lbwn_eval_nchunks(M);
+  double* vpart = nullptr;
+  a.rowv = nullptr;
+  if (by_voice) {
+    vpart = reinterpret_cast<double*>(sc + ev_up(sizeof(double) * 4 * (size_t)nb));
+    if (!nll)   // the voice pass reads the values back: from the caller's nll, else from the scratch rows
+      a.rowv = reinterpret_cast<float*>(sc + ev_up(sizeof(double) * 4 * (size_t)nb) +
+                                        ev_up(sizeof(double) * 2 * (size_t)nch * (size_t)n_bins));
+  }
+  if (Q <= 256) eval_head_kernel<4><<<nb, 256, 0, st>>>(a);
+  else if (Q <= 512) eval_head_kernel<8><<<nb, 256, 0, st>>>(a);
+  else eval_head_kernel<0><<<nb, 256, 0, st>>>(a);
+  LBWN_CHECK_LAUNCH();
+  if (by_voice) {
+    eval_voice_kernel<<<nch, 256, 0, st>>>(nll ? nll : a.rowv, nll ? ld_nll : (long)T, ids, B, T, n_bins, vpart);
+    LBWN_CHECK_LAUNCH();
+  }
+  eval_fold_kernel<<<1 + (by_voice ? (n_bins + 255) / 256 : 0), 256, 0, st>>>(a.partial, nb, acc, vpart, nch, n_bins,
+                                                                            by_voice, plan_status, status);
   LBWN_CHECK_LAUNCH();
   return 0;
 }

@@ -72,6 +72,17 @@ class AdamExArgs(ctypes.Structure):
         self.struct_size = ctypes.sizeof(AdamExArgs)
 
 
+class EvalArgs(ctypes.Structure):
+    """lbwn_eval_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('wav_q', c_fp), ('ids', c_fp), ('mel', c_fp), ('save', c_fp),
+                ('acc', c_fp), ('nll', c_fp), ('ld_nll', c_int64), ('by_voice', c_fp), ('n_bins', c_int),
+                ('status', c_fp), ('scratch', c_fp)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(EvalArgs)
+
+
 class MelCfg(ctypes.Structure):
     """lbwn_mel_cfg (include/lbwn.h), field for field; struct_size is set on construction."""
     _fields_ = [('struct_size', c_size_t), ('sample_rate', c_int), ('n_fft', c_int), ('win_length', c_int),
@@ -103,6 +114,8 @@ _SIGS = {
     'lbwn_train_forward': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_void_p]),
     'lbwn_train_backward': (c_int, [c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Params), c_fp, c_fp, c_fp,
                                     c_fp, c_void_p]),
+    'lbwn_train_eval_scratch_bytes': (c_size_t, [c_void_p, c_int]),
+    'lbwn_train_eval': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(EvalArgs), c_void_p]),
     'lbwn_adam_tf1': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int64, c_int64, c_float, c_float, c_float, c_float,
                               c_float, c_fp, c_fp, c_fp, c_void_p]),
     'lbwn_adam_ex_ws_floats': (c_int64, [c_int64]),

@@ -97,6 +97,73 @@ class SliceDealer:
         return batch[-1][0], wav, mel, ids
 
 
+def eval_batches(files, batch_sz, slice_sz, recep_field_sz, hop=1, n_mel=0, rows=None, log=None):
+    """A finite deal of a held-out catalogue for WaveNetTrain.evaluate: ``files`` (an iterable of
+    ``(vid, wav, mel)``) go through a SliceDealer once, in catalogue order, followed by all-masked
+    filler files (voice id 0, zeros) that let the slots still holding real samples finish their
+    slices.  The deal stops after the step in which the last non-zero id was dealt, so every
+    non-zero id of every file of length >= recep_field_sz is dealt exactly once; as in training, the
+    positions scored are those of them not in a slice's column 0 (a position is scored as the target
+    of the one before it in its slice).  Files shorter than the receptive field are skipped with the
+    dealer's warning, and so are files whose voice id is 0 (the mask value: nothing in them could be
+    scored, and dealt last they would add all-masked steps).  ``batch_sz`` is the GLOBAL batch;
+    ``rows`` (DPContext.rows) selects a rank's slots of each step, and every rank stops at the same step.
+    Yields (file_read_count, wav[B,T], mel[B,T/hop,n_mel] or None, ids[B,T])."""
+    log = log or sys.stderr
+    F = recep_field_sz
+    want_mel = n_mel > 0
+    state = {'expected': 0, 'done': False}
+    src = iter(files)
+
+    def usable():
+        for vid, wav, mel in src:
+            n = len(wav) - len(wav) % hop
+            if vid == 0:
+                print('Warning: skipping length {} wav file with voice id 0 (the mask value).'.format(n), file=log)
+                continue
+            if n < F:
+                print(('Warning: skipping length {} wav file (voice id {}).  '
+                       'Shorter than receptive field size of {}').format(n, vid, F), file=log)
+                continue
+            yield vid, wav, (mel if want_mel else None)
+
+    def chain():
+        it = usable()
+        nxt = next(it, None)
+        if nxt is None:
+            state['done'] = True
+        while nxt is not None:
+            cur, nxt = nxt, next(it, None)
+            n = len(cur[1]) - len(cur[1]) % hop
+            state['expected'] += n - (F - 1)
+            if nxt is None:
+                state['done'] = True     # the last real file is being handed out
+            yield cur
+        fill = max(slice_sz, F)
+        fill += -fill % hop
+        while True:
+            yield 0, np.zeros(fill, np.int32), (np.zeros((fill // hop, n_mel), np.float32) if want_mel else None)
+
+    feed = chain()
+    first = next(feed)          # decides 'done' for an empty catalogue before any step is dealt
+    if state['done'] and state['expected'] == 0:
+        return
+
+    def refeed():
+        yield first
+        yield from feed
+
+    dealer = SliceDealer(refeed(), batch_sz, slice_sz, F, hop, n_mel, log=log)
+    dealt = 0
+    while not (state['done'] and dealt >= state['expected']):
+        cnt, wav, mel, ids = next(dealer)
+        dealt += int(np.count_nonzero(ids))
+        if rows is not None:
+            wav, ids = wav[rows], ids[rows]
+            mel = mel[rows] if mel is not None else None
+        yield cnt, wav, mel, ids
+
+
 def npy_catalog(sam_file, repeat=True, shuffle_seed=None, skip=0):
     """data.py:43-48, :236-256: parse `vid \\t wav.npy \\t mel.npy` lines; repeat,
     shuffle (seeded) and skip `skip` files (resume position)."""

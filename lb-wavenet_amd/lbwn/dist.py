@@ -106,6 +106,22 @@ class DPContext:
         net.stats[:3].copy_(buf[n:n + 3])
         _reduce_status(net.status_word())
 
+    def reduce_eval(self, acc, by_voice=None, status=None):
+        """One SUM all-reduce of an evaluation's doubles (lbwn_train_eval's acc [4] and by_voice
+        [n_bins, 2]) after the last slice: every rank evaluated its rows of the same global deal, so
+        the sums are those of one process over the global batch.  The message is one contiguous
+        double buffer; ``status`` (the evaluation's int32 status word) takes the MAX like a step's."""
+        if not self.enabled:
+            return
+        parts = [acc.view(-1)] + ([by_voice.view(-1)] if by_voice is not None else [])
+        buf = torch.cat(parts) if len(parts) > 1 else parts[0]
+        dist.all_reduce(buf)
+        if len(parts) > 1:
+            acc.view(-1).copy_(buf[:acc.numel()])
+            by_voice.view(-1).copy_(buf[acc.numel():])
+        if status is not None:
+            _reduce_status(status)
+
     def _comm_stream(self, device):
         s = getattr(self, '_comm', None)
         if s is None:

@@ -204,6 +204,92 @@ class WaveNetTrain:
                                                     _lib.ptr(mel), sp))
         return self.stats
 
+    # ---- held-out evaluation (lbwn_train_eval) ---------------------------------
+    def eval_state(self, n_bins=None):
+        """The buffers one evaluation owns: a zero SAVE (its own D-sep state, never the training
+        run's), acc double[4], by_voice double[n_bins][2] when ``n_bins`` is given, the status word,
+        and the scratch, sized per slice length on first use."""
+        dev = self.device
+        return dict(save=torch.zeros_like(self.save_flat), acc=torch.zeros(4, dtype=torch.float64, device=dev),
+                    by_voice=(torch.zeros(int(n_bins), 2, dtype=torch.float64, device=dev)
+                              if n_bins is not None else None),
+                    n_bins=int(n_bins) if n_bins is not None else 0,
+                    status=torch.zeros(1, dtype=torch.int32, device=dev), scratch=None, keep=[])
+
+    def eval_slice(self, state, wav_input, lc_input, id_mask, flat=None, nll=None, stream=None):
+        """One lbwn_train_eval on a slice: adds to ``state`` (acc, by_voice, status) and advances its
+        SAVE.  ``nll``: an fp32 [B, >= T] device tensor to receive the per-position values.  No
+        synchronisation; the training run's save_flat, stats and counters are not touched."""
+        dev = self.device
+        if self.wav_input_type == 'raw':
+            from .ops import mu_encode
+            wav_input = mu_encode(torch.as_tensor(wav_input, dtype=torch.float32, device=dev), self.n_quant)
+        q = _i32(wav_input, dev)
+        ids = _i32(id_mask, dev)
+        B, T = q.shape
+        if B != self.batch_sz:
+            raise ValueError('batch %d != batch_sz %d' % (B, self.batch_sz))
+        mel = None
+        if self.use_lc_input():
+            mel = torch.as_tensor(lc_input, dtype=torch.float32, device=dev).contiguous()
+        h = self._plan(T)
+        need = self.lib.lbwn_train_eval_scratch_bytes(h, state['n_bins'])
+        if state['scratch'] is None or state['scratch'].numel() < need:
+            state['scratch'] = torch.empty(need, dtype=torch.uint8, device=dev)
+        params = self._params_c if flat is None else self._make_params_struct(flat)
+        a = _lib.EvalArgs(wav_q=q.data_ptr(), ids=ids.data_ptr(), mel=_lib.ptr(mel), save=state['save'].data_ptr(),
+                          acc=state['acc'].data_ptr(), nll=_lib.ptr(nll), ld_nll=nll.stride(0) if nll is not None else 0,
+                          by_voice=_lib.ptr(state['by_voice']), n_bins=state['n_bins'],
+                          status=state['status'].data_ptr(), scratch=state['scratch'].data_ptr())
+        state['keep'].append((q, ids, mel))   # inputs stay alive until the evaluation's synchronisation
+        _lib.check(self.lib.lbwn_train_eval(h, ctypes.byref(params), self._ws.data_ptr(), ctypes.byref(a),
+                                            _lib.stream_ptr(stream)))
+
+    def evaluate(self, batches, state=None, flat=None, want_nll=False):
+        """Held-out loss over an iterator of ``(cnt, wav, mel, ids)`` (lbwn.data.eval_batches): one
+        lbwn_train_eval per slice through one state, one synchronisation at the end.  ``flat``
+        selects another parameter buffer of the layout (the optimizer's EMA shadow); a ``state``
+        made with ``eval_state(n_bins)`` adds the per-voice split.  A state accumulates: the result
+        covers everything evaluated into it since eval_state().  Under data parallelism each rank
+        evaluates its rows of the same global deal and the sums are all-reduced once, into copies (the
+        state keeps the rank's own sums, so it stays reusable).  Returns
+        nll (mean, nats), bits (nll / ln 2), top1 (share with argmax == target), avg_diff (mean
+        |argmax - target|), n (scored positions), by_voice ([n_bins, 2]: sum, count) when the state has
+        bins, and with ``want_nll`` nll_rows (one fp32 [B, T] device tensor per slice).  Raises on a
+        nonzero status word."""
+        state = state if state is not None else self.eval_state()
+        if flat is not None and (flat.numel() != self.flat.numel() or flat.dtype != torch.float32
+                                 or flat.device != self.flat.device):
+            raise ValueError('flat must be an fp32 buffer of the parameter layout on the model device')
+        rows = []
+        for _, wav, mel, ids in batches:
+            out = None
+            if want_nll:
+                out = torch.zeros(np.shape(wav)[0], np.shape(wav)[1], dtype=torch.float32, device=self.device)
+                rows.append(out)
+            self.eval_slice(state, wav, mel, ids, flat=flat, nll=out)
+        acc, by_voice, status = state['acc'], state['by_voice'], state['status']
+        if self.dp is not None and self.dp.enabled:
+            # the global sums go into copies: the state keeps this rank's own, so it can be evaluated into again
+            acc, status = acc.clone(), status.clone()
+            by_voice = by_voice.clone() if by_voice is not None else None
+            self.dp.reduce_eval(acc, by_voice, status)
+        if self.device.type == 'cuda':
+            torch.cuda.synchronize(self.device)
+        state['keep'].clear()
+        st = int(status.item())
+        if st:
+            raise RuntimeError('lbwn: chain hand-off timed out during evaluation (status word %#x)' % st)
+        s, n, d, hit = acc.tolist()
+        mean = s / n if n else 0.0
+        res = dict(nll=mean, bits=mean / float(np.log(2.0)), top1=hit / n if n else 0.0,
+                   avg_diff=d / n if n else 0.0, n=int(n))
+        if by_voice is not None:
+            res['by_voice'] = by_voice.cpu().numpy()
+        if want_nll:
+            res['nll_rows'] = rows
+        return res
+
     def status_word(self, T=None):
         """int32 view of the plan's per-step status word (zeroed at each forward; the chains
         OR their timeout codes in: bit 0 forward chain, bit 1 backward chain)."""

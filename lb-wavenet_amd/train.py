@@ -16,6 +16,15 @@ each overrides the PAR_FILE key of the same name (clip_norm, ..., log_grad_norm;
 clipping or --log-grad-norm a second line follows each progress line:
 grad_norm, scale, lr and nonfinite_skips of the last applied step.
 
+Held-out evaluation (build extension, lbwn_train_eval): --valid-file names a second samples file; every
+--valid-interval steps (default 1000; the loop's step number, the one --save-interval counts and names
+checkpoints by, so a step that --skip-nonfinite left unapplied counts too), after the optimizer step, the
+whole file (or its first --valid-batches slices) is dealt once through the same plan with an evaluation
+state of its own, and rank 0 prints `valid <step> <nll> <bits> <top1> <avg_diff> <n>` (tab-separated) to
+stderr and appends it to <CKPT_PATH_PFX>.valid.tsv; --valid-ema adds a `valid_ema` line for the EMA
+shadows.  --eval-only (with --resume-step) restores, evaluates, prints and returns without a training
+step.  PAR_FILE keys: valid_file, valid_interval, valid_batches, valid_ema.
+
 TF-only switches are accepted for command-line compatibility: --tf-eager is implied,
 --add-summary/--tb-dir/--prof-dir/--timeline-file print what replaces them (rocprofv3),
 --tf-debug and --cpu-only exit(1) (there is no CPU execution path).
@@ -71,6 +80,17 @@ def get_args(argv=None):
     p.add_argument('--lr-decay-rate', type=float, metavar='FLOAT', help='(build extension) its rate, in (0, 1]')
     p.add_argument('--log-grad-norm', action='store_true', default=None,
                    help='(build extension) print the gradient norm with the progress line, without clipping')
+    p.add_argument('--valid-file', type=str, metavar='SAMPLES',
+                   help='(build extension) held-out samples file, evaluated every --valid-interval steps')
+    p.add_argument('--valid-interval', type=int, metavar='INT',
+                   help='(build extension) evaluate after the optimizer step of every INT-th step, counted like '
+                        '--save-interval (default 1000)')
+    p.add_argument('--valid-batches', type=int, metavar='INT',
+                   help='(build extension) evaluate only the first INT slices of the deal (default: all)')
+    p.add_argument('--valid-ema', action='store_true', default=None,
+                   help='(build extension) also evaluate the EMA shadows (needs --ema-decay)')
+    p.add_argument('--eval-only', action='store_true', default=False,
+                   help='(build extension) restore --resume-step, evaluate --valid-file, print and exit')
     p.add_argument('ckpt_path', type=str, metavar='CKPT_PATH_PFX')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('par_file', type=str, metavar='PAR_FILE')
@@ -92,12 +112,13 @@ def prepare_arch(arch, num_global_cond):
 
 OPT_KEYS = ('clip_norm', 'skip_nonfinite', 'ema_decay', 'lr_warmup_steps', 'lr_decay_steps', 'lr_decay_rate',
             'log_grad_norm')
+VALID_KEYS = ('valid_file', 'valid_interval', 'valid_batches', 'valid_ema')
 
 
 def override_par(args, par):
     """Command-line values replace the PAR_FILE's keys of the same name (a flag not given leaves the key)."""
     for flag, key in (('batch_size', 'batch_sz'), ('slice_size', 'slice_sz'), ('l2_factor', 'l2_factor'),
-                      ('learning_rate', 'learning_rate')) + tuple((k, k) for k in OPT_KEYS):
+                      ('learning_rate', 'learning_rate')) + tuple((k, k) for k in OPT_KEYS + VALID_KEYS):
         if getattr(args, flag) is not None:
             par[key] = getattr(args, flag)
     return par
@@ -109,6 +130,41 @@ def optimizer_kwargs(par):
                 skip_nonfinite=bool(par.get('skip_nonfinite', False)), ema_decay=par.get('ema_decay') or None,
                 warmup_steps=par.get('lr_warmup_steps', 0), decay_steps=par.get('lr_decay_steps', 0),
                 decay_rate=par.get('lr_decay_rate', 1.0), log_norm=bool(par.get('log_grad_norm', False)))
+
+
+def valid_options(par, eval_only=False):
+    """The held-out evaluation's options from the par dict: None without a valid_file, else
+    (file, interval, batches or None, ema).  Errors print to stderr and exit(1) like the others."""
+    vf = par.get('valid_file')
+    if not vf:
+        given = [k for k in VALID_KEYS[1:] if par.get(k) is not None and par.get(k) is not False]
+        if given or eval_only:
+            print('Error: --{} needs --valid-file'.format((given + ['eval_only'])[0].replace('_', '-')), file=sys.stderr)
+            sys.exit(1)
+        return None
+    interval = par.get('valid_interval')
+    interval = int(interval) if interval is not None else 1000
+    batches = par.get('valid_batches')
+    if interval < 1 or (batches is not None and int(batches) < 1):
+        print('Error: --valid-interval and --valid-batches must be >= 1', file=sys.stderr)
+        sys.exit(1)
+    ema = bool(par.get('valid_ema', False))
+    if ema and not par.get('ema_decay'):
+        print('Error: --valid-ema needs an EMA of the weights (--ema-decay)', file=sys.stderr)
+        sys.exit(1)
+    return vf, interval, int(batches) if batches is not None else None, ema
+
+
+def valid_files(sam_file, want_mel):
+    """The held-out catalogue's files in catalogue order, loaded as they are dealt."""
+    import numpy as np
+    with open(sam_file) as fh:
+        for line in fh:
+            line = line.strip()
+            if not line:
+                continue
+            vid, wav_path, mel_path = line.split('\t')
+            yield int(vid), np.load(wav_path), (np.load(mel_path).astype(np.float32) if want_mel else None)
 
 
 def main(argv=None):
@@ -140,11 +196,15 @@ def main(argv=None):
                   file=stderr)
 
     override_par(args, par)
+    valid = valid_options(par, args.eval_only)
+    if args.eval_only and not args.resume_step:
+        print('Error: --eval-only needs --resume-step', file=stderr)
+        sys.exit(1)
 
     import torch
     from lbwn import dist as lbdist
     from lbwn.arch import normalize_arch, mel_hop_sz as hop_of
-    from lbwn.data import DeviceBatches, MaskedSliceWav
+    from lbwn.data import DeviceBatches, MaskedSliceWav, eval_batches
     from lbwn.optim import AdamOptimizer
     from lbwn.tmodel import WaveNetTrain
 
@@ -191,6 +251,40 @@ def main(argv=None):
             skips_seen = optimizer.nonfinite_skips(net)
     dp.broadcast_params(net)
 
+    def validate(at_step):
+        """One deal of the held-out file through an evaluation state of its own (net.evaluate);
+        rank 0 prints and logs the line(s)."""
+        import io
+        import itertools
+        vf, _, vbatches, vema = valid
+        n_mel = arch['n_lc_in'] if arch['n_lc_out'] > 0 else 0
+        flats = [('valid', None)] + ([('valid_ema', optimizer.ex_slots(net)['ema'])] if vema else [])
+        for tag, flat in flats:
+            deal = eval_batches(valid_files(vf, n_mel > 0), B * dp.world, dset.slice_sz, net.get_recep_field_sz(),
+                                hop, n_mel, rows=dp.rows(B) if dp.enabled else None,
+                                log=stderr if not validate.warned and dp.rank == 0 else io.StringIO())
+            validate.warned = True   # the dealer's skipped-file warnings once, not per evaluation
+            r = net.evaluate(itertools.islice(deal, vbatches), flat=flat)
+            if dp.rank == 0:
+                line = '%s\t%d\t%.6f\t%.6f\t%.6f\t%.4f\t%d' % (tag, at_step, r['nll'], r['bits'], r['top1'],
+                                                                r['avg_diff'], r['n'])
+                print(line, file=stderr)
+                os.makedirs(os.path.dirname(os.path.abspath(args.ckpt_path)), exist_ok=True)
+                with open('{}.valid.tsv'.format(args.ckpt_path), 'a') as fh:
+                    fh.write(line + '\n')
+
+    validate.warned = False
+    if valid and arch['n_gc_embed'] > 0:
+        with open(valid[0]) as fh:
+            vmax = max([int(l.split('\t')[0]) for l in fh if l.strip()] or [0])
+        if vmax > arch['n_gc_category']:
+            print('Error: --valid-file has voice id {}, above n_gc_category {}'.format(vmax, arch['n_gc_category']),
+                  file=stderr)
+            sys.exit(1)
+    if args.eval_only:
+        validate(args.resume_step)
+        return net
+
     print('Starting training...', file=stderr)
     step = args.resume_step or 1
     itr = DeviceBatches(dset.get_itr(), net.device)   # pinned buffers, non-blocking H2D: no per-step sync
@@ -216,6 +310,8 @@ def main(argv=None):
                     skips - skips_seen), file=stderr)
                 skips_seen = skips
         optimizer.apply(net)
+        if valid and step % valid[1] == 0:
+            validate(step)
         if step % args.save_interval == 0 and step != args.resume_step:
             net.check_status()
             net_save_path = net.save(step, optimizer)        # collective under DP
