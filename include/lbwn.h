@@ -276,8 +276,8 @@ size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* plan);
  * densely as [B][n_frames·hop][n_lc_out], and "lccond" fp32 [NC][L][B][64] (slot = step mod NC;
  * columns: signal 0..31 | gate 32..63, zero past n_dil) and "pfcond" fp32 [B·T_s][G·2·n_dil], the
  * prefill's scratch (row b·T + j of a slice of T positions, layer l0 + g at column g·2·n_dil: signal
- * n_dil | gate n_dil; what the last projection launch of the last prefill left).  A name the plan
- * does not have is EINVAL. */
+ * n_dil | gate n_dil; what the last projection launch of the last prefill left).  Every plan also has
+ * "sessions" int64 [B][4], the words of lbwn_gen_begin (below).  A name the plan does not have is EINVAL. */
 int lbwn_gen_tensor(const lbwn_gen_plan* plan, const char* name, size_t* offset, size_t* bytes);
 /* Reset the state (zero lookback rings = imodel's zero-initialised buffers, step 0 input =
  * zero vector), load the teacher codes (device int32, may be NULL) and GC ids (device
@@ -302,7 +302,7 @@ int lbwn_gen_set_mel(lbwn_gen_plan* plan, const lbwn_params* params, void* works
  * resident: nothing else may occupy the device's CUs meanwhile.  LC plans split the call into
  * sub-runs of <= NC steps, each a projection launch (the sub-run's LC terms into "lccond") followed
  * by the step launches (persistent plans: one persistent launch per sub-run); EINVAL before any
- * launch when no mel is loaded. */
+ * launch when no mel is loaded or, after a lbwn_gen_begin, while a stream has begun no session. */
 int lbwn_gen_run(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, int n_steps, void* stream);
 /* 1 when the plan runs the persistent one-launch form (groups of <= 16 streams, each with its
  * own 32 head blocks, while every block fits on the device: B <= 80 on 256 CUs; layer/head sizes fit;
@@ -431,6 +431,59 @@ size_t lbwn_gen_state_bytes(const lbwn_gen_plan* plan, int n_streams);
 int lbwn_gen_state_save(const lbwn_gen_plan* plan, const void* workspace, void* state, void* stream);
 int lbwn_gen_state_load(lbwn_gen_plan* plan, void* workspace, const void* state, int state_streams,
                         const int* src_stream, void* stream);
+/* Sessions: begin a new utterance in single streams between two lbwn_gen_run calls while the other
+ * streams continue (added after ABI 5 was declared, same ABI: one symbol added, none altered; DESIGN
+ * §4.29).  With t0 the device step counter at the call (read on the device), every listed stream b = slot
+ * is afterwards in the state lbwn_gen_start leaves a stream in -- zero rings, the zero vector as pending
+ * input (code -1), PRE_BIAS as lbwn_gen_start's pre_bias says -- and in addition has
+ *   a step origin and a draw key: base_b = t0, key_b = key.  Its local step at absolute step t is
+ *     i = t - base_b and its uniform splitmix64(seed, key_b, i) >> 40 / 2^24: an utterance draws the same
+ *     whichever stream carries it and whenever it starts.  lbwn_gen_start stands for base_b = 0, key_b = b.
+ *   GC archs: its rows of the GC projection table recomputed from gc_id, bitwise what lbwn_gen_start
+ *     writes for that id.
+ *   LC archs: its own mel, run through the plan's upsample stack (the fused launch inside its envelope,
+ *     else one GEMM per stage) into the stream's own region of "lc", which in this mode is
+ *     [B][reserved rows][n_lc_out]; local step i is conditioned on local row min(max(i - 1, 0),
+ *     n_frames·hop - 1), lbwn_gen_set_mel's rule per session.
+ * "samples" and "wav" stay [B][max_steps] indexed by the absolute step: a session's j-th sample is column
+ * base_b + j.  The other streams, their "logits", the step counter, "status", the hand-off granules and the
+ * sampling settings are untouched.  A run does not outlive max_steps: size it for the whole schedule.
+ * The words live in "sessions", int64 [B][4] = {base, key, rows = n_frames·hop, 0}: the last 32·B bytes
+ * (rounded up to 256) of the workspace, over the tail of the prefill scratch, so the workspace size of a
+ * plan is what it was (a plan whose prefill scratch is smaller than the words grows by the difference).
+ * Their content is defined from the first begin after lbwn_gen_start, which also writes {0, b, 0, 0} for the
+ * streams it does not list.  Until that begin the draw and the projection take no table: the kernels
+ * launched and the bits drawn are those of a build without this call.
+ * One call is one reset-and-GC launch for all listed streams (one per 128 of them) plus each stream's
+ * upsample launches; stream-ordered, no allocation, no host synchronisation.  s is host memory, read at
+ * the call; each mel is device memory that must stay valid until its upsample launches have run.
+ * A captured lbwn_gen_run is bound to the mode it was captured in, in both directions: the capture bakes in
+ * whether the draw and the LC projection take the words.  One captured in session mode (after the first
+ * begin) stays valid across later begins, whose words are read on the device, but must not be replayed
+ * after a lbwn_gen_start until a begin has put the run back into session mode; one captured on the dense
+ * path must not be replayed after a begin.  Replaying across a mode change raises no error: it draws and
+ * projects from the wrong words.  Capture again instead.
+ * Modes between two lbwn_gen_start calls: on LC plans lbwn_gen_set_mel and lbwn_gen_begin exclude each
+ * other (EINVAL for the later one), and after a begin lbwn_gen_run is EINVAL until every stream has begun a
+ * session.  Plans without LC may begin any subset at any time.  lbwn_gen_prefill and lbwn_gen_score are
+ * EINVAL after a begin: both stay whole-batch operations (and they overwrite "sessions").
+ * lbwn_gen_state_save / _load work as documented and do not carry the words: an identity rewind with no
+ * begin in between repeats the run.
+ * EINVAL before any launch, naming the argument: a null plan, params, workspace or s; struct_size !=
+ * sizeof(lbwn_gen_session); n < 1 or n > batch_sz; a teacher loaded by lbwn_gen_start (n_teacher > 0: the
+ * override is keyed by the absolute step); a slot outside [0, batch_sz) or listed twice; a key outside
+ * [0, 2^31); gc_id outside [0, n_gc_category] on a GC arch (ignored without GC); on an LC arch mel NULL
+ * or not 16-byte aligned, n_frames < 1 or n_frames·hop beyond the plan's reserved rows; mel non-NULL on
+ * an arch without LC. */
+typedef struct lbwn_gen_session {
+  int slot;          /* stream index in [0, batch_sz) */
+  int gc_id;         /* GC archs: voice id in [0, n_gc_category]; ignored without GC */
+  int64_t key;       /* the draw's stream key, 0 <= key < 2^31 */
+  const float* mel;  /* LC archs: device fp32 [n_frames][n_lc_in], 16-B aligned; must be NULL without LC */
+  int64_t n_frames;  /* LC archs: >= 1, n_frames*hop <= the plan's reserved rows; 0 without LC */
+} lbwn_gen_session;
+int lbwn_gen_begin(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const lbwn_gen_session* s,
+                   int n, size_t struct_size, void* stream);
 
 /* ---- log-mel front end: wav to the LC conditioning, one launch (added after ABI 5 was declared, same
  * ABI: symbols added, none altered) ----

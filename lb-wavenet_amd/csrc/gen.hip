@@ -31,12 +31,16 @@
 // Teacher-forced scoring (lbwn_gen_score): the same host loop with every layer's z kept side by side
 // in a caller-owned Zcat, the per-step GEMM form's head over all rows of a slice, and one wave per
 // row for logp = logit[code] - logsumexp (gen_score_logp_kernel).
+// Sessions (lbwn_gen_begin): single streams restarted between two runs -- gen_begin_kernel zeroes their
+// rings, rewrites their GC rows and writes their words {base, key, rows}; the draw and the LC projection
+// read the words when the plan hands them the table, the chains know nothing of it.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "kernels.h"
@@ -443,6 +447,8 @@ struct DrawK {
   float* logits; int* samples; float* wav; long long max_steps;
   const int* teacher; long long n_teacher; unsigned long long seed; int* code;
   float temperature; int top_k; float top_p;   // lbwn_gen_set_sampling; read by the FILT forms only
+  // sessions (lbwn_gen_begin): [B][4] int64 {base, key, rows, 0}, or null: key = stream, base = 0
+  const long long* sess;
 };
 
 // wave-wide max / min / inclusive scan on DPP (row ops + row_bcast, GFX9): one VALU latency
@@ -527,6 +533,13 @@ template <int MP>
 LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool write, bool decode = true) {
   const int lane = threadIdx.x & 63, Q = a.Q;
   const int per = (Q + 63) >> 6, c0 = lane * per;
+  // the draw's key: (stream, absolute step), or the session's (key, local step t - base); the two words
+  // are fetched here, ahead of the max / exp / scan they are needed after
+  uint64_t skey = (uint64_t)b, sstep = (uint64_t)t;
+  if (a.sess) {
+    skey = (uint64_t)a.sess[4 * b + 1];
+    sstep = (uint64_t)(t - a.sess[4 * b]);
+  }
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < MP; ++j) {
@@ -544,7 +557,7 @@ LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool 
   const float incl = wave_scan(loc);
   const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
   const float excl = incl - loc;
-  const uint64_t h = splitmix(a.seed, (uint64_t)b, (uint64_t)t);
+  const uint64_t h = splitmix(a.seed, skey, sstep);
   const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
   const float target = u * total;
   int found = Q;   // the lane whose run contains the crossing point
@@ -590,6 +603,13 @@ template <int MP>
 LBWN_DEV int draw_core_filt(float (&v)[MP], const DrawK& a, int b, long long t, bool write, bool decode = true) {
   const int lane = threadIdx.x & 63, Q = a.Q;
   const int per = (Q + 63) >> 6, c0 = lane * per;
+  // the draw's key: (stream, absolute step), or the session's (key, local step t - base); the two words
+  // are fetched here, ahead of the max / exp / scan they are needed after
+  uint64_t skey = (uint64_t)b, sstep = (uint64_t)t;
+  if (a.sess) {
+    skey = (uint64_t)a.sess[4 * b + 1];
+    sstep = (uint64_t)(t - a.sess[4 * b]);
+  }
   float mx = -INFINITY;
   unsigned key[MP];
 #pragma unroll
@@ -640,7 +660,7 @@ LBWN_DEV int draw_core_filt(float (&v)[MP], const DrawK& a, int b, long long t, 
   const float incl = wave_scan(loc);
   const float total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
   const float excl = incl - loc;
-  const uint64_t h = splitmix(a.seed, (uint64_t)b, (uint64_t)t);
+  const uint64_t h = splitmix(a.seed, skey, sstep);
   const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
   const float target = u * total;
   int found = Q, lastc = -1;   // lastc: this lane's last surviving code (e > 0 only on codes < Q)
@@ -1217,18 +1237,24 @@ __global__ __launch_bounds__(512) void gen_persist_kernel(PersistK a) {
 }
 
 // gc_proj[l][b][o] = GC_EMBED[gc_id[b]] · [GC_SIGNAL_l | GC_GATE_l]  (imodel.py:53-56, :113-118)
+// one element (the sum in k order; gen_begin_kernel forms a restarted stream's row with the same code)
+LBWN_DEV float gc_proj_elem(const float* emb, const float* gsig, const float* ggate, int id, int l, int o, int Ge,
+                            int Cd) {
+  const int oc = o & 31;
+  float s = 0.f;
+  if (oc < Cd) {
+    const float* G = (o < 32 ? gsig : ggate) + (long)l * Ge * Cd;
+    const float* em = emb + (long)id * Ge;
+    for (int k = 0; k < Ge; ++k) s += em[k] * G[k * Cd + oc];
+  }
+  return s;
+}
 __global__ void gen_gc_proj_kernel(const float* emb, const float* gsig, const float* ggate, const int* ids,
                                    float* out, int B, int Ge, int Cd) {
   const int l = blockIdx.x;
   for (int e = threadIdx.x; e < B * 64; e += blockDim.x) {
-    const int b = e / 64, o = e % 64, oc = o & 31;
-    float s = 0.f;
-    if (oc < Cd) {
-      const float* G = (o < 32 ? gsig : ggate) + (long)l * Ge * Cd;
-      const float* em = emb + (long)ids[b] * Ge;
-      for (int k = 0; k < Ge; ++k) s += em[k] * G[k * Cd + oc];
-    }
-    out[((long)l * B + b) * 64 + o] = s;
+    const int b = e / 64, o = e % 64;
+    out[((long)l * B + b) * 64 + o] = gc_proj_elem(emb, gsig, ggate, ids[b], l, o, Ge, Cd);
   }
 }
 
@@ -1242,6 +1268,8 @@ __global__ void gen_gc_proj_kernel(const float* emb, const float* gsig, const fl
 // one output column, plain f32 FMAs in k order (the lc rows staged in LDS and read as broadcasts,
 // the weight column coalesced over o and read once per 64 rows).  t and n_rows come from device words, so the launch is
 // capturable and a replayed graph follows a mel loaded later.
+// SESS (lbwn_gen_begin): every stream has its own region of "lc" (lc_stride rows apart) and its own
+// step origin and row count in the session words: r = min(max(t - base_b - 1, 0), rows_b - 1).
 constexpr int LCP_KT = 128;   // k tile staged per pass
 constexpr int LCP_ROWS = 64, LCP_RPT = LCP_ROWS / 4;   // rows per block / per thread
 
@@ -1249,19 +1277,33 @@ struct LcProjK {
   const float* lc; const float* wsig; const float* wgate; float* out;
   const long long* step; const int* n_rows;
   int B, L, Lo, Cd, NC, n;
+  const long long* sess; long lc_stride;   // SESS only
 };
 
+template <bool SESS>
 __global__ __launch_bounds__(256) void gen_lc_proj_kernel(LcProjK a) {
   __shared__ __attribute__((aligned(16))) float xs[LCP_ROWS][LCP_KT];
   const int tid = threadIdx.x, l = blockIdx.x, m0 = blockIdx.y * LCP_ROWS, M = a.n * a.B;
   const long long t0 = *a.step;
-  const int n_rows = max(*a.n_rows, 1);
+  const int n_rows = SESS ? 1 : max(*a.n_rows, 1);
   const int o = tid & 63, oc = o & 31, rq = tid >> 6;
   const bool ocv = oc < a.Cd;
   const float* W = (o < 32 ? a.wsig : a.wgate) + (long)l * a.Lo * a.Cd + min(oc, a.Cd - 1);
   float acc[LCP_RPT];
 #pragma unroll
   for (int r = 0; r < LCP_RPT; ++r) acc[r] = 0.f;
+  // SESS: each block row's lc row index once, through LDS (the words are two dependent loads ahead of
+  // the row's address otherwise, for every float4 of the row)
+  __shared__ long srow[SESS ? LCP_ROWS : 1];
+  if (SESS) {
+    if (tid < LCP_ROWS) {
+      const int m = min(m0 + tid, M - 1), b = m % a.B;
+      const long long rows = max(a.sess[4 * b + 2], 1LL);
+      const long long r = min(max(t0 + m / a.B - a.sess[4 * b] - 1, 0LL), rows - 1);
+      srow[tid] = (long)b * a.lc_stride + (long)r;
+    }
+    __syncthreads();
+  }
   for (int k0 = 0; k0 < a.Lo; k0 += LCP_KT) {
     const int kt = min(LCP_KT, a.Lo - k0), kt4 = kt >> 2;   // Lo is a multiple of 4
     if (k0) __syncthreads();
@@ -1269,8 +1311,12 @@ __global__ __launch_bounds__(256) void gen_lc_proj_kernel(LcProjK a) {
       const int j = e / kt4, k = 4 * (e % kt4), m = min(m0 + j, M - 1);
       const int b = m % a.B;
       const long long t = t0 + m / a.B;
-      const long long r = min(max(t - 1, 0LL), (long long)n_rows - 1);
-      *(floatx4*)&xs[j][k] = *(const floatx4*)(a.lc + ((long)b * n_rows + r) * a.Lo + k0 + k);
+      if (SESS) {
+        *(floatx4*)&xs[j][k] = *(const floatx4*)(a.lc + srow[j] * a.Lo + k0 + k);
+      } else {
+        const long long r = min(max(t - 1, 0LL), (long long)n_rows - 1);
+        *(floatx4*)&xs[j][k] = *(const floatx4*)(a.lc + ((long)b * n_rows + r) * a.Lo + k0 + k);
+      }
     }
     __syncthreads();
     for (int k = 0; k < kt; k += 4) {
@@ -1308,6 +1354,48 @@ __global__ void gen_reset_kernel(float* rings, long n_ring, unsigned long long* 
       *step = 0;
       *status = 0;
     }
+  }
+}
+
+// ---- sessions (lbwn_gen_begin) --------------------------------------------------
+// Restart the listed streams between two runs: block (l, i) zeroes stream slot[i]'s [d_l][Cr] block of
+// ring l and forms its GC projection row of layer l (gen_gc_proj_kernel's sum); block (0, i) also writes
+// the stream's session words {base = *step, key, rows, 0} and its pending code -1 (the zero vector).
+// init_all (the first begin since lbwn_gen_start): block (0, 0) gives every stream the launch does not
+// list the words lbwn_gen_start stands for, {0, b, 0, 0}.  The list travels in the kernel arguments
+// (host memory read at the call, no copy): GB_MAX entries per launch.
+constexpr int GB_MAX = 128;
+struct BeginK {
+  float* rings; int* code; const long long* step; long long* sess;
+  const float* emb; const float* gsig; const float* ggate; float* gcp;   // emb null: no GC
+  int B, L, nbl, Cr, Ge, Cd, n, init_all;
+  int slot[GB_MAX], gc_id[GB_MAX], key[GB_MAX], rows[GB_MAX];
+};
+
+__global__ __launch_bounds__(256) void gen_begin_kernel(BeginK a) {
+  const int l = blockIdx.x, i = blockIdx.y, b = a.slot[i];
+  long roff = 0;   // ring offset of layer l
+  for (int k = 0; k < l; ++k) roff += (long)(1 << (k % a.nbl)) * a.B * a.Cr;
+  const int d = 1 << (l % a.nbl);
+  float* ring = a.rings + roff + (long)b * d * a.Cr;
+  for (int e = threadIdx.x; e < d * a.Cr; e += blockDim.x) ring[e] = 0.f;
+  if (a.emb) {
+    for (int o = threadIdx.x; o < 64; o += blockDim.x)
+      a.gcp[((long)l * a.B + b) * 64 + o] = gc_proj_elem(a.emb, a.gsig, a.ggate, a.gc_id[i], l, o, a.Ge, a.Cd);
+  }
+  if (l != 0) return;
+  if (i == 0 && a.init_all) {
+    for (int s = threadIdx.x; s < a.B; s += blockDim.x) {
+      bool listed = false;
+      for (int j = 0; j < a.n; ++j) listed |= a.slot[j] == s;
+      if (!listed) {
+        a.sess[4 * s] = 0; a.sess[4 * s + 1] = s; a.sess[4 * s + 2] = 0; a.sess[4 * s + 3] = 0;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.sess[4 * b] = *a.step; a.sess[4 * b + 1] = a.key[i]; a.sess[4 * b + 2] = a.rows[i]; a.sess[4 * b + 3] = 0;
+    a.code[b] = -1;
   }
 }
 
@@ -1752,6 +1840,14 @@ struct lbwn_gen_plan {
   int pfT = 0, pfH = 0, pfG = 0;
   size_t oPFX[2] = {0, 0}, oPFZ = 0, oPFIMG = 0, oPFGC = 0, oPFIDS = 0, oPFCOND = 0;
   int ncu = 0;   // the device's CUs at plan creation (0: none seen), the state copies' grid
+  // sessions (lbwn_gen_begin): the words "sessions" int64 [B][4] at the very end of the workspace, over
+  // the tail of the prefill scratch (prefill and score are refused in session mode, and the first begin
+  // since lbwn_gen_start writes every stream's words); host-tracked like mel_loaded: a begin happened
+  // since lbwn_gen_start, and which streams have begun a session
+  size_t oSESS = 0;
+  bool sess_mode = false;
+  std::vector<unsigned char> sess_begun, sess_seen;
+  int n_begun = 0;
 };
 
 constexpr int G_LC_CHUNK = 64;         // default NC (steps per projection launch / persistent sub-run)
@@ -1909,6 +2005,15 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
       p->oPFCOND = gcarve(cur, 4 * (size_t)B * p->pfT * p->pfG * 2 * p->Cd);
     }
   }
+  {   // "sessions": the last 32·B bytes (rounded up to 256) of the workspace.  They lie over the prefill
+      // scratch, which no call reads in session mode, so a plan's workspace keeps its size; only a plan
+      // whose prefill scratch is smaller than the words (a degenerate slice) grows by the difference
+    const size_t sb = (32 * (size_t)B + 255) / 256 * 256;
+    if (cur - p->oPFX[0] < sb) gcarve(cur, sb - (cur - p->oPFX[0]));
+    p->oSESS = cur - sb;
+    p->sess_begun.assign(B, 0);
+    p->sess_seen.assign(B, 0);
+  }
   p->total = cur;
   *out = p;
   return 0;
@@ -1931,6 +2036,7 @@ extern "C" int lbwn_gen_tensor(const lbwn_gen_plan* p, const char* name, size_t*
   else if (!strcmp(name, "teacher")) { *off = p->oTEACH; *bytes = 4 * (size_t)std::max<long long>(1, p->n_teacher); }
   else if (p->Lo > 0 && !strcmp(name, "lc")) { *off = p->oLC; *bytes = 4 * B * (size_t)p->lc_rows * p->Lo; }
   else if (p->Lo > 0 && !strcmp(name, "lccond")) { *off = p->oLCC; *bytes = 4 * (size_t)p->NC * p->L * B * 64; }
+  else if (!strcmp(name, "sessions")) { *off = p->oSESS; *bytes = 32 * B; }
   else if (p->Lo > 0 && !strcmp(name, "pfcond")) { *off = p->oPFCOND; *bytes = 4 * B * (size_t)p->pfT * p->pfG * 2 * p->Cd; }
   else LBWN_REQUIRE(false, "gen_tensor: unknown tensor '%s'", name);
   return 0;
@@ -1950,6 +2056,9 @@ extern "C" int lbwn_gen_start(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
   hipStream_t st = (hipStream_t)stream;
   p->n_teacher = teacher ? n_teacher : 0;
   p->mel_loaded = false;
+  p->sess_mode = false;
+  p->n_begun = 0;
+  std::fill(p->sess_begun.begin(), p->sess_begun.end(), 0);
   p->seed = seed;
   p->pre_bias = pre_bias;
   gen_reset_kernel<<<256, 256, 0, st>>>(gat<float>(ws, p->oRING), p->n_ring, gat<unsigned long long>(ws, p->oGRAN),
@@ -1975,6 +2084,29 @@ extern "C" int lbwn_gen_start(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
   return 0;
 }
 
+// the plan's upsample stack over `frames` mel frames [frames][Li] into act[i] (stage i's output; the last
+// is the lc rows): the fused launcher inside its envelope, else one GEMM per stage
+static int gen_upsample(const lbwn_gen_plan* p, const lbwn_params* P, const float* mel, long long frames,
+                        float* const* act, hipStream_t st) {
+  if (p->up_fused) return lbwn_lc_up_fwd_launch(p->nup, p->up, p->Li, p->Lo, (int)frames, mel, P->lc_up, act, st);
+  // per-stage GEMMs against the [s][O][I] filters read as k-contiguous (engine.cpp cond_forward)
+  const float* in = mel;
+  long long rows = frames;
+  int I = p->Li;
+  for (int i = 0; i < p->nup; ++i) {
+    const int s = p->up[i];
+    lbwn_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.A = in; g.lda = I; g.B = P->lc_up[i]; g.ldb = I; g.C = act[i]; g.ldc = (long)s * p->Lo;
+    g.M = (int)rows; g.N = s * p->Lo; g.K = I;
+    if (int e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st)) return e;
+    in = act[i];
+    rows *= s;
+    I = p->Lo;
+  }
+  return 0;
+}
+
 extern "C" int lbwn_gen_set_mel(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const float* mel, int64_t n_frames,
                                 void* stream) {
   LBWN_REQUIRE(p && P && ws, "gen_set_mel: null argument");
@@ -1985,29 +2117,14 @@ extern "C" int lbwn_gen_set_mel(lbwn_gen_plan* p, const lbwn_params* P, void* ws
                (long long)n_frames, p->hop, p->lc_rows);
   LBWN_REQUIRE(P->lc_sig && P->lc_gate, "gen_set_mel: LC_SIGNAL/LC_GATE pointers are null");
   for (int i = 0; i < p->nup; ++i) LBWN_REQUIRE(P->lc_up[i], "gen_set_mel: LC_UPSAMPLE_%d pointer is null", i);
+  LBWN_REQUIRE(!p->sess_mode, "gen_set_mel: the run is in session mode (lbwn_gen_begin since lbwn_gen_start); the "
+               "mels come with the sessions");
   hipStream_t st = (hipStream_t)stream;
   const long long frames = (long long)p->B * n_frames;
   LBWN_REQUIRE(frames * p->hop < (1LL << 31), "gen_set_mel: too many rows");
   float* act[8];
   for (int i = 0; i < p->nup; ++i) act[i] = gat<float>(ws, p->oLCACT[i]);
-  if (p->up_fused) {
-    if (int e = lbwn_lc_up_fwd_launch(p->nup, p->up, p->Li, p->Lo, (int)frames, mel, P->lc_up, act, st)) return e;
-  } else {   // per-stage GEMMs against the [s][O][I] filters read as k-contiguous (engine.cpp cond_forward)
-    const float* in = mel;
-    long long rows = frames;
-    int I = p->Li;
-    for (int i = 0; i < p->nup; ++i) {
-      const int s = p->up[i];
-      lbwn_gemm_args g;
-      memset(&g, 0, sizeof(g));
-      g.A = in; g.lda = I; g.B = P->lc_up[i]; g.ldb = I; g.C = act[i]; g.ldc = (long)s * p->Lo;
-      g.M = (int)rows; g.N = s * p->Lo; g.K = I;
-      if (int e = lbwn_gemm_launch(g, 1, 1, 1, nullptr, st)) return e;
-      in = act[i];
-      rows *= s;
-      I = p->Lo;
-    }
-  }
+  if (int e = gen_upsample(p, P, mel, frames, act, st)) return e;
   gen_set_word_kernel<<<1, 1, 0, st>>>(gat<int>(ws, p->oSTEP + 12), (int)(n_frames * p->hop));
   LBWN_CHECK_LAUNCH();
   p->mel_loaded = true;
@@ -2103,6 +2220,7 @@ static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_s
   d.max_steps = p->max_steps; d.teacher = gat<int>(ws, p->oTEACH); d.n_teacher = p->n_teacher; d.seed = p->seed;
   d.code = gat<int>(ws, p->oCODE);
   d.temperature = p->temperature; d.top_k = p->top_k; d.top_p = p->top_p;
+  d.sess = p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr;
   if (p->persist) {
     if (n_steps == 0) return 0;
     PersistK k;
@@ -2176,7 +2294,11 @@ static int gen_run_sub(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_s
 
 extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_steps, void* stream) {
   LBWN_REQUIRE(p && P && ws && n_steps >= 0, "gen_run: bad arguments");
-  LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded, "gen_run: LC plan without a mel (lbwn_gen_set_mel after lbwn_gen_start)");
+  LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded || p->sess_mode,
+               "gen_run: LC plan without a mel (lbwn_gen_set_mel after lbwn_gen_start)");
+  LBWN_REQUIRE(p->Lo == 0 || !p->sess_mode || p->n_begun == p->B,
+               "gen_run: session mode, but only %d of the %d streams have begun a session (lbwn_gen_begin gives "
+               "each its mel)", p->n_begun, p->B);
   hipStream_t st = (hipStream_t)stream;
   if (p->Lo == 0) {
     if (int e = gen_run_sub(p, P, ws, n_steps, st)) return e;
@@ -2186,9 +2308,12 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
     k.lc = gat<float>(ws, p->oLC); k.wsig = P->lc_sig; k.wgate = P->lc_gate; k.out = gat<float>(ws, p->oLCC);
     k.step = gat<long long>(ws, p->oSTEP); k.n_rows = gat<int>(ws, p->oSTEP + 12);
     k.B = p->B; k.L = p->L; k.Lo = p->Lo; k.Cd = p->Cd; k.NC = p->NC;
+    k.sess = p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr; k.lc_stride = (long)p->lc_rows;
     for (int done = 0; done < n_steps; done += p->NC) {
       k.n = std::min(p->NC, n_steps - done);
-      gen_lc_proj_kernel<<<dim3(p->L, (k.n * p->B + LCP_ROWS - 1) / LCP_ROWS), 256, 0, st>>>(k);
+      const dim3 grid(p->L, (k.n * p->B + LCP_ROWS - 1) / LCP_ROWS);
+      if (p->sess_mode) gen_lc_proj_kernel<true><<<grid, 256, 0, st>>>(k);
+      else gen_lc_proj_kernel<false><<<grid, 256, 0, st>>>(k);
       LBWN_CHECK_LAUNCH();
       if (int e = gen_run_sub(p, P, ws, k.n, st)) return e;
     }
@@ -2202,6 +2327,87 @@ extern "C" int lbwn_gen_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, in
   return 0;
 }
 
+// ---- sessions: restart single streams between two runs -------------------------------------------
+extern "C" int lbwn_gen_begin(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const lbwn_gen_session* s, int n,
+                              size_t struct_size, void* stream) {
+  LBWN_REQUIRE(p, "gen_begin: plan is null");
+  LBWN_REQUIRE(P, "gen_begin: params is null");
+  LBWN_REQUIRE(ws, "gen_begin: workspace is null");
+  LBWN_REQUIRE(s, "gen_begin: s (the session array) is null");
+  LBWN_REQUIRE(struct_size == sizeof(lbwn_gen_session), "gen_begin: struct_size %zu != %zu", struct_size,
+               sizeof(lbwn_gen_session));
+  LBWN_REQUIRE(n >= 1 && n <= p->B, "gen_begin: n = %d sessions must be in 1..batch_sz = %d", n, p->B);
+  LBWN_REQUIRE(p->n_teacher == 0, "gen_begin: lbwn_gen_start loaded a teacher of n_teacher = %lld codes; the teacher "
+               "override is keyed by the absolute step and sessions do not take it", p->n_teacher);
+  LBWN_REQUIRE(!(p->mel_loaded && !p->sess_mode), "gen_begin: lbwn_gen_set_mel loaded a dense mel since "
+               "lbwn_gen_start; the two modes are exclusive");
+  const bool gc = p->a.n_gc_embed > 0, lc = p->Lo > 0;
+  if (lc) {
+    LBWN_REQUIRE(P->lc_sig && P->lc_gate, "gen_begin: LC_SIGNAL/LC_GATE pointers are null");
+    for (int i = 0; i < p->nup; ++i) LBWN_REQUIRE(P->lc_up[i], "gen_begin: LC_UPSAMPLE_%d pointer is null", i);
+  }
+  if (gc) LBWN_REQUIRE(P->gc_embed && P->gc_sig && P->gc_gate, "gen_begin: GC_EMBED/GC_SIGNAL/GC_GATE pointers are null");
+  const long long max_frames = lc ? p->lc_rows / p->hop : 0;
+  std::vector<unsigned char>& seen = p->sess_seen;   // sized at plan creation: no allocation here
+  std::fill(seen.begin(), seen.end(), 0);
+  for (int i = 0; i < n; ++i) {
+    LBWN_REQUIRE(s[i].slot >= 0 && s[i].slot < p->B, "gen_begin: s[%d].slot = %d is outside [0, batch_sz = %d)", i,
+                 s[i].slot, p->B);
+    LBWN_REQUIRE(!seen[s[i].slot], "gen_begin: s[%d].slot = %d is listed twice", i, s[i].slot);
+    seen[s[i].slot] = 1;
+    LBWN_REQUIRE(s[i].key >= 0 && s[i].key < (1LL << 31), "gen_begin: s[%d].key = %lld is outside [0, 2^31)", i,
+                 (long long)s[i].key);
+    LBWN_REQUIRE(!gc || (s[i].gc_id >= 0 && s[i].gc_id <= p->a.n_gc_category),
+                 "gen_begin: s[%d].gc_id = %d is outside [0, n_gc_category = %d]", i, s[i].gc_id, p->a.n_gc_category);
+    if (lc) {
+      LBWN_REQUIRE(s[i].mel, "gen_begin: s[%d].mel is null on an LC arch", i);
+      LBWN_REQUIRE((((uintptr_t)s[i].mel) & 15) == 0, "gen_begin: s[%d].mel %p is not 16-byte aligned", i,
+                   (const void*)s[i].mel);
+      LBWN_REQUIRE(s[i].n_frames >= 1 && s[i].n_frames <= max_frames,
+                   "gen_begin: s[%d].n_frames = %lld must be in 1..%lld (x hop %lld within the plan's %lld rows)", i,
+                   (long long)s[i].n_frames, max_frames, p->hop, p->lc_rows);
+    } else {
+      LBWN_REQUIRE(!s[i].mel, "gen_begin: s[%d].mel is given, but the arch has no local conditioning", i);
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < n; i0 += GB_MAX) {
+    BeginK k;
+    memset(&k, 0, sizeof(k));
+    k.rings = gat<float>(ws, p->oRING); k.code = gat<int>(ws, p->oCODE); k.step = gat<long long>(ws, p->oSTEP);
+    k.sess = gat<long long>(ws, p->oSESS);
+    if (gc) { k.emb = P->gc_embed; k.gsig = P->gc_sig; k.ggate = P->gc_gate; k.gcp = gat<float>(ws, p->oGCP); }
+    k.B = p->B; k.L = p->L; k.nbl = p->nbl; k.Cr = p->Cr; k.Ge = p->a.n_gc_embed; k.Cd = p->Cd;
+    k.n = std::min(GB_MAX, n - i0);
+    k.init_all = !p->sess_mode && i0 == 0;
+    for (int i = 0; i < k.n; ++i) {
+      const lbwn_gen_session& e = s[i0 + i];
+      k.slot[i] = e.slot; k.gc_id[i] = gc ? e.gc_id : 0; k.key[i] = (int)e.key;
+      k.rows[i] = lc ? (int)(e.n_frames * p->hop) : 0;
+    }
+    gen_begin_kernel<<<dim3(p->L, k.n), 256, 0, st>>>(k);
+    LBWN_CHECK_LAUNCH();
+  }
+  p->sess_mode = true;
+  for (int i = 0; i < n; ++i) {
+    if (!p->sess_begun[s[i].slot]) { p->sess_begun[s[i].slot] = 1; ++p->n_begun; }
+  }
+  if (lc) {
+    const long long max_fr = p->lc_rows / p->hop;
+    for (int i = 0; i < n; ++i) {   // the stream's own region of "lc" and of the stages' scratch
+      float* act[8];
+      long long r = max_fr;
+      for (int j = 0; j + 1 < p->nup; ++j) {
+        r *= p->up[j];
+        act[j] = gat<float>(ws, p->oLCACT[j]) + (size_t)s[i].slot * r * p->Lo;
+      }
+      act[p->nup - 1] = gat<float>(ws, p->oLC) + (size_t)s[i].slot * p->lc_rows * p->Lo;
+      if (int e = gen_upsample(p, P, s[i].mel, s[i].n_frames, act, st)) return e;
+    }
+  }
+  return 0;
+}
+
 // ---- parallel prompt prefill ----------------------------------------------------------------
 // the refusals lbwn_gen_prefill and lbwn_gen_score share (what: the call's name in the message)
 static int prefill_check(const char* what, const lbwn_gen_plan* p, const lbwn_params* P, const void* ws,
@@ -2210,6 +2416,8 @@ static int prefill_check(const char* what, const lbwn_gen_plan* p, const lbwn_pa
   LBWN_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
   LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "%s: ld_codes %lld must be 0 (one shared vector) or >= n = %lld", what,
                (long long)ld_codes, (long long)n);
+  LBWN_REQUIRE(!p->sess_mode, "%s: not supported in session mode (lbwn_gen_begin since lbwn_gen_start): it is a "
+               "whole-batch operation", what);
   LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded,
                "%s: local conditioning is not supported before lbwn_gen_set_mel (no mel loaded)", what);
   LBWN_REQUIRE(p->Lo == 0 || (P->lc_sig && P->lc_gate), "%s: LC_SIGNAL/LC_GATE pointers are null", what);

@@ -25,6 +25,11 @@ prefill='fanout')); with --mel-npy only the shared [frames, n_lc_in] shape.
 --teacher-prefill.  --score-npy PATH saves the [batch, n] float32 log-probabilities.
 --ema (build extension) loads every variable from its exponential moving average in the checkpoint
 (train.py --ema-decay); a checkpoint without them is an error.
+--mel-list LIST (build extension, LC archs only) vocodes a list: every line is "vid<TAB>mel.npy[<TAB>name]",
+and OUTPUT_WAV_DIR/<name>.wav gets frames x hop samples for every line (WaveNetGen.vocode: a stream of the
+batch takes the next utterance as soon as its own is covered; the draw key is the line's position, so a wav
+does not depend on --batch-size).  A list whose outputs, upsampled mels and upsample scratch would exceed
+--mel-list-budget-mb on the device is vocoded in consecutive groups.
 """
 import argparse
 import json
@@ -76,6 +81,16 @@ def get_args(argv=None):
     p.add_argument('--mel-config', type=str, default=None, metavar='JSON',
                    help='(build extension) with --mel-from-wav: the mel_config.json make_mels.py wrote; its hop '
                         'and n_mels must equal the arch\'s')
+    p.add_argument('--mel-list', type=str, default=None, metavar='LIST',
+                   help='(build extension) vocode a list: every LIST line is "vid<TAB>mel.npy[<TAB>name]" (voice '
+                        'id, a .npy of [frames, n_lc_in], the output name; default: the mel file\'s stem); writes '
+                        'OUTPUT_WAV_DIR/<name>.wav of frames x hop samples for every line.  The batch\'s streams '
+                        'are recycled as utterances end (WaveNetGen.vocode); --gen-seconds, the teacher options '
+                        'and --mel-npy / --mel-from-wav do not apply')
+    p.add_argument('--mel-list-budget-mb', type=float, default=4096.0, metavar='MB',
+                   help='(build extension) with --mel-list: the most the outputs, the upsampled mels and the '
+                        'upsample stages\' scratch of one run may take on the device; a longer list is vocoded '
+                        'in consecutive groups')
     p.add_argument('--temperature', type=float, default=1.0,
                    help='(build extension) softmax temperature of the draw, finite and > 0 (1 = off)')
     p.add_argument('--top-k', type=int, default=0,
@@ -118,6 +133,133 @@ def load_teacher(path, sample_rate, start=None, duration=None):
     return x
 
 
+def mel_list_bytes(total, batch_sz, n_lc_out, lc_upsample):
+    """Device bytes a session run of ``total`` steps holds per plan in "samples", "wav" (4 bytes per stream
+    and step each), "lc" (ceil(total / hop) frames x hop rows of n_lc_out floats per stream) and the
+    upsample stack's scratch (the output of every stage before the last: frames x the product of the
+    strides so far rows of n_lc_out floats per stream)."""
+    hop = 1
+    for s in lc_upsample:
+        hop *= int(s)
+    frames = -(-total // hop)
+    rows, r = frames * hop, frames
+    for s in list(lc_upsample)[:-1]:
+        r *= int(s)
+        rows += r
+    return batch_sz * (8 * total + 4 * n_lc_out * rows)
+
+
+def mel_list_groups(lengths, batch_sz, chunk, n_lc_out, lc_upsample, budget):
+    """Consecutive groups of utterance indices, each as long as its schedule (plan_sessions) keeps
+    mel_list_bytes within ``budget``; an utterance that alone exceeds it is a group of its own."""
+    from lbwn.imodel import plan_sessions
+    groups, cur = [], []
+    for u in range(len(lengths)):
+        total = plan_sessions([lengths[v] for v in cur + [u]], batch_sz, chunk)[1]
+        if cur and mel_list_bytes(total, batch_sz, n_lc_out, lc_upsample) > budget:
+            groups.append(cur)
+            cur = []
+        cur.append(u)
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def read_mel_list(path, n_lc_in, n_gc_category):
+    """[(voice id, mel [frames, n_lc_in] float32, name)] of a --mel-list file; ValueError naming the line."""
+    import numpy as np
+    out, names = [], set()
+    with open(path) as fp:
+        for ln, line in enumerate(fp, 1):
+            line = line.rstrip('\n')
+            if not line.strip():
+                continue
+            f = line.split('\t')
+            if len(f) not in (2, 3):
+                raise ValueError('line %d: expected "vid<TAB>mel.npy[<TAB>name]", got %r' % (ln, line))
+            try:
+                vid = int(f[0])
+            except ValueError:
+                raise ValueError('line %d: voice id %r is not an integer' % (ln, f[0]))
+            if n_gc_category and not 0 <= vid <= n_gc_category:
+                raise ValueError('line %d: voice id %d is outside [0, %d]' % (ln, vid, n_gc_category))
+            try:
+                mel = np.load(f[1], allow_pickle=False)
+            except (OSError, ValueError) as e:
+                raise ValueError('line %d: cannot read mel %s: %s' % (ln, f[1], e))
+            if mel.ndim != 2 or mel.shape[1] != n_lc_in or mel.shape[0] < 1:
+                raise ValueError('line %d: mel %s has shape %s, expected [frames, %d]'
+                                 % (ln, f[1], tuple(mel.shape), n_lc_in))
+            name = f[2].strip() if len(f) == 3 and f[2].strip() else os.path.splitext(os.path.basename(f[1]))[0]
+            if name in names or os.sep in name:
+                raise ValueError('line %d: output name %r is taken by an earlier line or is not a file name'
+                                 % (ln, name))
+            names.add(name)
+            out.append((vid, np.ascontiguousarray(mel, np.float32), name))
+    if not out:
+        raise ValueError('no utterances listed')
+    return out
+
+
+def main_mel_list(args, arch):
+    """--mel-list: vocode every line of the list through WaveNetGen.vocode, one wav per line."""
+    from sys import stderr
+    import numpy as np
+    from lbwn.arch import mel_hop_sz
+    from lbwn.ckpt import ckpt_file
+    from lbwn.imodel import WaveNetGen
+    if args.mel_npy is not None or args.mel_from_wav is not None or args.teacher_wav is not None:
+        print('--mel-list takes its mels from LIST: not with --mel-npy, --mel-from-wav or --teacher-wav',
+              file=stderr)
+        sys.exit(1)
+    if arch['n_lc_out'] == 0:
+        print('--mel-list: ARCH_FILE has no local conditioning, there is nothing to vocode from', file=stderr)
+        sys.exit(1)
+    if not os.access(args.mel_list, os.R_OK):
+        print("Couldn't find mel list {}".format(args.mel_list), file=stderr)
+        sys.exit(1)
+    try:
+        utts = read_mel_list(args.mel_list, arch['n_lc_in'], arch['n_gc_category'] if arch['n_gc_embed'] else 0)
+    except ValueError as e:
+        print('--mel-list {}: {}'.format(args.mel_list, e), file=stderr)
+        sys.exit(1)
+    if not os.access(ckpt_file(args.ckpt), os.R_OK):
+        print("Couldn't find checkpoint file {}".format(ckpt_file(args.ckpt)), file=stderr)
+        sys.exit(1)
+    hop = mel_hop_sz(arch)
+    lengths = [m.shape[0] * hop for _, m, _ in utts]
+    groups = mel_list_groups(lengths, args.batch_size, args.chunk_size, arch['n_lc_out'], arch['lc_upsample'],
+                             int(args.mel_list_budget_mb * 2 ** 20))
+    net = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
+                     arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
+                     args.batch_size, args.chunk_size, None, seed=args.seed, n_lc_in=arch['n_lc_in'],
+                     n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'], temperature=args.temperature,
+                     top_k=args.top_k, top_p=args.top_p)
+    print('Restoring from {}'.format(args.ckpt))
+    try:
+        net.restore(args.ckpt, ema=args.ema)
+    except ValueError as e:
+        if not args.ema:
+            raise
+        print('--ema: {}'.format(e), file=stderr)
+        sys.exit(1)
+    from scipy.io import wavfile
+    os.makedirs(args.wav_dir, exist_ok=True)
+    print('Vocoding {} utterances in {} group(s).'.format(len(utts), len(groups)))
+    wavs = [None] * len(utts)
+    for grp in groups:
+        # the draw keys are the list positions: a wav does not depend on the batch size or the grouping
+        out = net.vocode([utts[u][1] for u in grp], gc_ids=[utts[u][0] for u in grp] if arch['n_gc_embed'] else None,
+                         keys=grp)
+        for u, w in zip(grp, out):
+            wavs[u] = w.cpu().numpy().astype(np.float32)
+            path = os.path.join(args.wav_dir, utts[u][2] + '.wav')
+            wavfile.write(path, args.sample_rate, wavs[u])
+            print('Wrote {}'.format(path))
+    print('Finished.')
+    return wavs
+
+
 def main(argv=None):
     args = get_args(argv)
     from sys import stderr
@@ -152,6 +294,8 @@ def main(argv=None):
         sys.exit(1)
     with open(args.arch_file) as fp:
         arch = normalize_arch(json.load(fp))
+    if args.mel_list is not None:
+        return main_mel_list(args, arch)
     mel_cfg = None
     if args.mel_from_wav is not None:
         if arch['n_lc_out'] == 0:

@@ -94,6 +94,11 @@ class MelCfg(ctypes.Structure):
         self.struct_size = ctypes.sizeof(MelCfg)
 
 
+class GenSession(ctypes.Structure):
+    """lbwn_gen_session (include/lbwn.h), field for field."""
+    _fields_ = [('slot', c_int), ('gc_id', c_int), ('key', c_int64), ('mel', c_fp), ('n_frames', c_int64)]
+
+
 _SIGS = {
     'lbwn_mel_plan_create': (c_int, [ctypes.POINTER(MelCfg), ctypes.POINTER(c_void_p)]),
     'lbwn_mel_plan_destroy': (None, [c_void_p]),
@@ -129,6 +134,8 @@ _SIGS = {
     'lbwn_gen_set_mel': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_void_p]),
     'lbwn_gen_run': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_int, c_void_p]),
     'lbwn_gen_is_persistent': (c_int, [c_void_p]),
+    'lbwn_gen_begin': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(GenSession), c_int, c_size_t,
+                               c_void_p]),
     'lbwn_gen_prefill': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_void_p]),
     'lbwn_gen_score_scratch_bytes': (c_size_t, [c_void_p]),
     'lbwn_gen_score': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_fp, c_int64, c_fp,

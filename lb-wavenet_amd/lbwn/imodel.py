@@ -36,6 +36,13 @@ pending codes and the step of every stream, stream-major, so it loads into a pla
 ``load_state(state, streams)`` gives stream b the record ``streams[b]``; ``fork(src)`` is both at once.
 ``run(gen_sz, prefill='fanout')`` prefills the teacher once per distinct voice id in a private generator
 and loads that state into every stream of the voice.
+
+Sessions (lbwn_gen_begin): ``begin(slots, mels, gc_ids, keys)`` restarts single streams between
+two ``step`` calls -- zero rings, the stream's own mel, voice id, draw key and step origin -- while the others
+continue; ``take(slot, n)`` is a session's first n samples of "wav".  ``vocode(mels)`` turns a list of mels of
+different lengths into one wav each, recycling a stream as soon as its utterance is covered (the schedule of
+``plan_sessions``); with the default keys (the utterance indices) the result does not depend on batch_sz or
+on the schedule.
 """
 import ctypes
 import math
@@ -75,6 +82,40 @@ def parse_state_header(raw):
     if h['n_streams'] < 1 or h['record_bytes'] != state_record_bytes(h['n_blocks'], h['n_block_layers'], h['n_res']):
         raise ValueError('state: inconsistent header %r' % (h,))
     return h
+
+
+def plan_sessions(lengths, batch_sz, chunk):
+    """The schedule ``WaveNetGen.vocode`` runs: utterances of ``lengths[u]`` steps dealt to ``batch_sz``
+    slots first in, first out, a slot taking the next utterance at the first chunk boundary after its
+    own is covered.  Returns (rounds, total): each round is (steps to run, [(slot, utterance), ...] to
+    begin before them), total the sum of the steps -- what the plan's max_steps must hold.  While
+    utterances wait a round runs a whole ``chunk``; once none waits, min(chunk, the longest remainder).
+    Pure host arithmetic."""
+    lens = [int(n) for n in lengths]
+    if isinstance(batch_sz, bool) or not isinstance(batch_sz, (int, np.integer)) or batch_sz < 1:
+        raise ValueError('plan_sessions: batch_sz must be an integer >= 1, got %r' % (batch_sz,))
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError('plan_sessions: chunk must be an integer >= 1, got %r' % (chunk,))
+    for u, n in enumerate(lens):
+        if n < 1:
+            raise ValueError('plan_sessions: lengths[%d] = %d must be >= 1' % (u, n))
+    left = [0] * int(batch_sz)      # steps each slot's session still needs
+    rounds, total, nxt = [], 0, 0
+    while True:
+        begins = []
+        for slot in range(int(batch_sz)):
+            if left[slot] <= 0 and nxt < len(lens):
+                begins.append((slot, nxt))
+                left[slot] = lens[nxt]
+                nxt += 1
+        need = max(left)
+        if need <= 0:
+            break
+        steps = int(chunk) if nxt < len(lens) else min(int(chunk), need)
+        rounds.append((steps, begins))
+        total += steps
+        left = [r - steps for r in left]
+    return rounds, total
 
 
 class GenState:
@@ -148,12 +189,21 @@ class WaveNetGen:
         self._plan = None
         self._ws = None
         self._graph = None
+        self._graph_mode = None   # (session mode, steps) the captured chunk was captured with
         self._mel = None      # the mel loaded by the last init_buffers (None: none since lbwn_gen_start)
         self._started = False   # init_buffers (lbwn_gen_start) ran on the current plan
         self._state_keep = None   # the snapshot and map of the last load_state: its launch reads them in stream order
         self._fan = None        # (n_voices, n), the private generator of the last fan-out prefill
         self.teacher_logp = None   # [batch_sz, n] of the last init_buffers(prefill='score')
         self._score_scratch = None   # (plan, uint8 tensor): lbwn_gen_score's scratch, allocated once per plan
+        self._reset_sessions()
+
+    def _reset_sessions(self):
+        """Host mirror of what lbwn_gen_start resets: no session mode, the step 0, no stream has a base."""
+        self._sess_mode = False          # a begin since the last lbwn_gen_start
+        self._hstep = 0                  # the device step counter, tracked on the host (None: unknown)
+        self._base = [None] * self.batch_sz   # each slot's step origin
+        self._sess_mels = {}             # slot -> the device mel its upsample launches read
 
     # ---- parameters -------------------------------------------------------------------------
     def load_params(self, src, ema=False):
@@ -215,6 +265,7 @@ class WaveNetGen:
         self._params_c = P
         self._graph = None
         self._started = False
+        self._reset_sessions()
         self._apply_sampling()
         return self
 
@@ -320,6 +371,8 @@ class WaveNetGen:
         _lib.check(self.lib.lbwn_gen_prefill(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                              self._prefill_codes.data_ptr(), n if codes.dim() == 2 else 0, n,
                                              _lib.stream_ptr()))
+        if self._hstep is not None:
+            self._hstep += n
         return n
 
     def score(self, codes):
@@ -343,6 +396,8 @@ class WaveNetGen:
         _lib.check(self.lib.lbwn_gen_score(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
                                            self._prefill_codes.data_ptr(), n if codes.dim() == 2 else 0, n,
                                            logp.data_ptr(), n, self._score_scratch[1].data_ptr(), _lib.stream_ptr()))
+        if self._hstep is not None:
+            self._hstep += n
         return logp
 
     # ---- state ------------------------------------------------------------------------------
@@ -399,6 +454,7 @@ class WaveNetGen:
         self._state_keep = (blob, mt)
         _lib.check(self.lib.lbwn_gen_state_load(self._plan, self._ws.data_ptr(), blob.data_ptr(), state.n_streams,
                                                 _lib.ptr(mt), _lib.stream_ptr()))
+        self._hstep = None        # the snapshot's step: read from the device when a begin needs it
         return self
 
     def fork(self, src):
@@ -478,6 +534,7 @@ class WaveNetGen:
                                            _lib.ptr(self._gc), _lib.ptr(t), 0 if t is None else t.numel(),
                                            self.seed, int(self.pre_bias), _lib.stream_ptr()))
         self._mel = None      # lbwn_gen_start clears the loaded mel
+        self._reset_sessions()
         if mel is not None:
             if not isinstance(mel, torch.Tensor):
                 mel = torch.from_numpy(np.array(mel, np.float32))   # a writable copy (a broadcast view is not)
@@ -509,8 +566,14 @@ class WaveNetGen:
         """Advance every stream by n_steps samples (graph replay of chunk_sz-step chunks)."""
         chunk = self.chunk_sz
         done = 0
+        # a captured chunk is bound to what its capture baked in: the number of steps, and whether the draw
+        # and the LC projection take the session words (session mode) or not (the dense path).  A later
+        # lbwn_gen_start or begin that changes the mode makes it draw from the wrong table: capture again.
+        if self._graph is not None and self._graph_mode != (self._sess_mode, chunk):
+            self._graph = None
         if self.use_graph and n_steps >= chunk:
             if self._graph is None:
+                self._graph_mode = (self._sess_mode, chunk)
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 g = torch.cuda.CUDAGraph()
@@ -526,6 +589,8 @@ class WaveNetGen:
                 done += chunk
         if n_steps - done > 0:
             self._launch(n_steps - done)
+        if self._hstep is not None:
+            self._hstep += int(n_steps)
 
     def run(self, gen_sz, gc_ids=None, mel=None, prefill=False):
         """The reference's sess.run(wave_ops) (generate.py:110): generate gen_sz steps from a
@@ -562,3 +627,183 @@ class WaveNetGen:
 
     def logits(self):
         return self.tensor('logits').view(self.batch_sz, self.arch['n_quant'])
+
+    # ---- sessions ---------------------------------------------------------------------------
+    def init_sessions(self):
+        """lbwn_gen_start for a run whose streams all get their voice and mel from ``begin``: no teacher,
+        voice id 0 everywhere until a session says otherwise, no dense mel."""
+        if self._plan is None:
+            raise RuntimeError('init_sessions: no plan (build_graph first)')
+        self._gc = None
+        if self.arch['n_gc_embed'] > 0:
+            self._gc = torch.zeros(self.batch_sz, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.lbwn_gen_start(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(),
+                                           _lib.ptr(self._gc), None, 0, self.seed, int(self.pre_bias),
+                                           _lib.stream_ptr()))
+        self._mel = None
+        self._reset_sessions()
+        self._started = True
+        return self
+
+    def _check_begin(self, slots, mels, gc_ids, keys):
+        """(slots, mels, gc_ids, keys) as lists of equal length, validated; ValueError naming the argument.
+        No library call."""
+        try:
+            slots = list(slots)
+        except TypeError:
+            raise ValueError('begin: slots must be a list of stream indices, got %r' % (slots,))
+        n = len(slots)
+        if not 1 <= n <= self.batch_sz:
+            raise ValueError('begin: %d slots given, expected 1..batch_sz = %d' % (n, self.batch_sz))
+        for i, b in enumerate(slots):
+            if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch_sz:
+                raise ValueError('begin: slots[%d] = %r is not an integer in [0, %d)' % (i, b, self.batch_sz))
+        if len(set(int(b) for b in slots)) != n:
+            raise ValueError('begin: slots %r lists a stream twice' % (slots,))
+        keys = list(slots) if keys is None else list(keys)
+        if len(keys) != n:
+            raise ValueError('begin: keys has %d entries for %d slots' % (len(keys), n))
+        for i, k in enumerate(keys):
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < 2 ** 31:
+                raise ValueError('begin: keys[%d] = %r is not an integer in [0, 2^31)' % (i, k))
+        if self.arch['n_gc_embed'] > 0:
+            if gc_ids is None:
+                raise ValueError('begin: GC arch, gc_ids (one voice id per slot) required')
+            gc_ids = list(gc_ids)
+            if len(gc_ids) != n:
+                raise ValueError('begin: gc_ids has %d entries for %d slots' % (len(gc_ids), n))
+            for i, v in enumerate(gc_ids):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or \
+                        not 0 <= v <= self.arch['n_gc_category']:
+                    raise ValueError('begin: gc_ids[%d] = %r is not a voice id in [0, %d]'
+                                     % (i, v, self.arch['n_gc_category']))
+        else:
+            gc_ids = [0] * n
+        if self.arch['n_lc_out'] == 0:
+            if mels is not None:
+                raise ValueError('begin: mels given, but the arch has no local conditioning')
+            mels = [None] * n
+        else:
+            if mels is None:
+                raise ValueError('begin: LC arch, mels (one [n_frames, n_lc_in] per slot) required')
+            mels = list(mels)
+            if len(mels) != n:
+                raise ValueError('begin: mels has %d entries for %d slots' % (len(mels), n))
+            mels = [self._as_mel(m, 'begin: mels[%d]' % i) for i, m in enumerate(mels)]
+        return [int(b) for b in slots], mels, [int(v) for v in gc_ids], [int(k) for k in keys]
+
+    def _as_mel(self, m, what):
+        """One utterance's mel as a tensor or float32 array [n_frames, n_lc_in] (a nested list is converted);
+        ValueError naming ``what`` otherwise."""
+        if not isinstance(m, torch.Tensor):
+            try:
+                m = np.asarray(m, np.float32)
+            except (TypeError, ValueError):
+                raise ValueError('%s is not an array of numbers [n_frames, %d]' % (what, self.arch['n_lc_in']))
+        shp = tuple(m.shape)
+        if len(shp) != 2 or shp[1] != self.arch['n_lc_in'] or shp[0] < 1:
+            raise ValueError('%s has shape %s, expected [n_frames, %d]' % (what, shp, self.arch['n_lc_in']))
+        return m
+
+    def begin(self, slots, mels=None, gc_ids=None, keys=None):
+        """Begin a new utterance in the streams ``slots`` at the current step while the others continue
+        (lbwn_gen_begin, on the current stream): each gets zero rings, its mel ``mels[i]`` [n_frames,
+        n_lc_in] (LC archs), its voice ``gc_ids[i]`` (GC archs) and the draw key ``keys[i]`` (default: the
+        slot), and counts its steps from here.  After init_buffers without a mel or teacher, or
+        init_sessions; an LC plan runs again once every stream has begun a session.  A captured chunk is
+        bound to the mode of its capture: one captured before the first begin is dropped (it draws without
+        the session words), one captured in session mode stays valid across later begins and is dropped by
+        ``step`` once init_buffers / init_sessions has left session mode."""
+        slots, mels, gc_ids, keys = self._check_begin(slots, mels, gc_ids, keys)
+        if self._plan is None or not self._started:
+            raise RuntimeError('begin: no run (build_graph, then init_sessions or init_buffers)')
+        if self._hstep is None:       # after a load_state: the snapshot's step
+            self._hstep = int(self.tensor('step', torch.int64).item())
+        arr = (_lib.GenSession * len(slots))()
+        keep = {}
+        for i, b in enumerate(slots):
+            arr[i].slot, arr[i].gc_id, arr[i].key = b, gc_ids[i], keys[i]
+            if mels[i] is not None:
+                m = mels[i]
+                if not isinstance(m, torch.Tensor):
+                    m = torch.from_numpy(np.ascontiguousarray(m, np.float32))
+                keep[b] = m.to(device=self.device, dtype=torch.float32).contiguous()
+                arr[i].mel, arr[i].n_frames = keep[b].data_ptr(), keep[b].shape[0]
+        _lib.check(self.lib.lbwn_gen_begin(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(), arr,
+                                           len(slots), ctypes.sizeof(_lib.GenSession), _lib.stream_ptr()))
+        self._sess_mels.update(keep)     # read by the upsample launches in stream order
+        if not self._sess_mode:
+            self._graph = None
+            self._sess_mode = True
+        for b in slots:
+            self._base[b] = self._hstep
+        return self
+
+    def take(self, slot, n):
+        """The first n samples of the session stream ``slot`` carries: "wav" columns base .. base + n - 1
+        (a view; the steps must have run)."""
+        if self._plan is None or not 0 <= slot < self.batch_sz or self._base[slot] is None:
+            raise ValueError('take: stream %r has begun no session' % (slot,))
+        b0 = self._base[slot]
+        if n < 0 or b0 + n > self.max_steps:
+            raise ValueError('take: %d samples from step %d exceed max_steps %d' % (n, b0, self.max_steps))
+        return self.tensor('wav').view(self.batch_sz, self.max_steps)[slot, b0:b0 + n]
+
+    def vocode(self, mels, gc_ids=None, keys=None, chunk=None):
+        """One wav per mel: ``mels`` is a list of [n_frames_u, n_lc_in] arrays of any lengths; utterance u
+        gets n_frames_u·hop samples, voice ``gc_ids[u]`` (GC archs) and draw key ``keys[u]`` (default u, so
+        the wavs do not depend on batch_sz or on the schedule).  Runs ``plan_sessions(lengths, batch_sz,
+        chunk)`` (chunk defaults to chunk_sz and holds for this call only): a stream takes the next utterance
+        at the first chunk boundary after its own is covered.  Returns the wavs, float32 tensors on the device, in input order."""
+        if self.arch['n_lc_out'] == 0:
+            raise ValueError('vocode: the arch has no local conditioning (nothing to vocode from)')
+        mels = list(mels)
+        if not mels:
+            return []
+        chunk = self.chunk_sz if chunk is None else int(chunk)
+        n_utt = len(mels)
+        keys = list(range(n_utt)) if keys is None else list(keys)
+        if len(keys) != n_utt:
+            raise ValueError('vocode: keys has %d entries for %d mels' % (len(keys), n_utt))
+        if self.arch['n_gc_embed'] > 0:
+            if gc_ids is None or len(list(gc_ids)) != n_utt:
+                raise ValueError('vocode: GC arch, gc_ids (one voice id per mel) required')
+            gc_ids = [int(v) for v in gc_ids]
+        mels = [self._as_mel(m, 'vocode: mels[%d]' % u) for u, m in enumerate(mels)]
+        lengths = [int(m.shape[0]) * self.hop for m in mels]
+        rounds, total = plan_sessions(lengths, self.batch_sz, chunk)
+        if self._plan is None or self.max_steps < total:
+            self.build_graph(total)
+        keep_chunk = self.chunk_sz       # ``chunk`` holds for this call only (step re-captures on a change)
+        self.chunk_sz = chunk
+        try:
+            return self._vocode_rounds(mels, gc_ids, keys, lengths, rounds)
+        finally:
+            self.chunk_sz = keep_chunk
+
+    def _vocode_rounds(self, mels, gc_ids, keys, lengths, rounds):
+        """vocode's schedule on the built plan: one lbwn_gen_start, then per round its begins and its steps."""
+        n_utt = len(mels)
+        self.init_sessions()
+        where = [None] * n_utt           # (slot, base) of every utterance
+        idle = np.zeros((1, self.arch['n_lc_in']), np.float32)   # streams no utterance ever reaches
+        for r, (steps, begins) in enumerate(rounds):
+            slots = [s for s, _ in begins]
+            ms = [mels[u] for _, u in begins]
+            ks = [int(keys[u]) for _, u in begins]
+            gs = [gc_ids[u] for _, u in begins] if gc_ids is not None else None
+            if r == 0:
+                for s in range(len(begins), self.batch_sz):
+                    slots.append(s)
+                    ms.append(idle)
+                    ks.append(0)
+                    if gs is not None:
+                        gs.append(0)
+            if slots:
+                self.begin(slots, ms, gs, ks)
+            for s, u in begins:
+                where[u] = (s, self._base[s])
+            self.step(steps)
+        self.check_status()
+        wav = self.tensor('wav').view(self.batch_sz, self.max_steps)
+        return [wav[s, b0:b0 + lengths[u]].clone() for u, (s, b0) in enumerate(where)]

@@ -157,7 +157,9 @@ class WaveNetTrain:
             self._plans[T] = (h, nbytes)
         h, nbytes = self._plans[T]
         if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            # zeroed once, at allocation: the padding rows that plan_tensor reports but no launch writes
+            # (e.g. "dz" in whole 32-row blocks) are then defined, not whatever the allocator handed back
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         return h
 
     def plan_tensor(self, T, name):
