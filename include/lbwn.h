@@ -82,7 +82,9 @@ int lbwn_plan_tensor(const lbwn_plan* plan, const char* name, size_t* offset, si
  * images: the bf16-split forward chain computes the LC term itself), "split_dlc", "split_dlcx",
  * "split_dlct", "split_up0" .. "split_up7" (split-K counts of dLCcat, dlc, dLCcatᵀ and the per-stage
  * filter gradients; 0 for a stage the arch does not have), and, valid after a backward, "dv_blk" (DV
- * was exported k-blocked) and "dlc_parts" (split-K partials dlc left for the fused upsample backward).
+ * was exported k-blocked) and "dlc_parts" (split-K partials dlc left for the fused upsample backward);
+ * "dmel_fused", valid after a lbwn_train_backward_ex that wrote dmel: 1 = the fused upsample backward
+ * wrote it, 0 = a GEMM after the per-stage products, -1 before any such backward.
  * An unknown key is EINVAL. */
 int lbwn_plan_info(const lbwn_plan* plan, const char* key, int64_t* value);
 /* One-shot timing probe: the next lbwn_train_forward/backward on this plan records
@@ -122,6 +124,36 @@ int lbwn_train_forward(lbwn_plan* plan, const lbwn_params* params, void* workspa
  * workspace/stream.  grads: every pointer of the struct is fully overwritten. */
 int lbwn_train_backward(lbwn_plan* plan, const lbwn_params* params, const lbwn_params* grads, void* workspace,
                         const int* wav_q, const int* ids, const float* mel, void* stream);
+
+/* lbwn_train_backward with optional outputs (added after ABI 5 was declared, same ABI: symbols added,
+ * none altered).  wav_q, ids and mel are lbwn_train_backward's.
+ *   dmel  nullable device fp32 [B][T/hop][n_lc_in], dense, 16-byte aligned, fully overwritten: the
+ *         gradient with respect to the mel input of the same quantity as every other gradient of this
+ *         call -- Σ masked xent, NOT divided by n_valid, no l2 term.  With dlc [B·T][n_lc_out] the gradient
+ *         into the upsample stack's output (the sum of the dlc product's split-K partials),
+ *           d(in_i)[t][c] = Σ_{j,o} d(out_i)[s_i·t + j][o]·F_i[j][o][c],  i = nup-1 .. 0,  dmel = d(in_0).
+ *         Kernel = stride, so a frame's row depends only on the hop rows of dlc under it: no atomics, a
+ *         summation order the shapes alone fix, two calls give the same bits.  A frame that lies wholly
+ *         after its stream's last scored position (position t is scored iff ids[b][t+1] != 0) is exactly 0.
+ *         Written by the fused upsample backward (plans with "up_fused_bwd") or by one more product after
+ *         the per-stage GEMMs; lbwn_plan_info "dmel_fused" says which.  It must not alias mel, the
+ *         gradients or the workspace, and is final when the call's work on `stream` is, like the gradients.
+ * With dmel NULL the call is lbwn_train_backward: the same launches, the same bits.  The workspace size
+ * of every plan is what it was without this call.
+ * EINVAL before any launch and before the device is touched, naming the argument: every refusal of
+ * lbwn_train_backward (a null plan, params, grads, workspace, wav_q or ids; mel NULL on an LC arch; no
+ * training forward on the plan, as after lbwn_train_eval; a GEMM mode changed since the forward); a null
+ * a; struct_size != sizeof(lbwn_backward_args); dmel on an arch without LC; dmel not 16-byte aligned;
+ * dmel overlapping mel or the workspace. */
+typedef struct lbwn_backward_args {
+  size_t struct_size;
+  const int* wav_q;
+  const int* ids;
+  const float* mel;
+  float* dmel;
+} lbwn_backward_args;
+int lbwn_train_backward_ex(lbwn_plan* plan, const lbwn_params* params, const lbwn_params* grads, void* workspace,
+                           const lbwn_backward_args* a, void* stream);
 
 /* Held-out evaluation of one slice (added after ABI 5 was declared, same ABI: two symbols added, none
  * altered).  Runs lbwn_train_forward's forward up to the raw logits [B·T][n_quant] -- the
@@ -656,6 +688,10 @@ int lbwn_gemm_form_query(int which, int M, int N, int K, int a_kcontig, int pres
  *   (a multiple of 4, >= frames·hop·Lo; unused for one part), the mel and the stage inputs
  *   act[0 .. nup-2] (act[nup-1] is not read and may be NULL).  Per-frame partials go to dpart and are
  *   summed in frame order (deterministic).
+ * lbwn_lc_upsample_backward_dmel: the same, and dmel [frames][Li] (required, overwritten) = stage 0's
+ *   input gradient, d(in_0)[f][c] = Σ_{j,o} d(out_0)[s_0·f + j][o]·F_0[j][o][c], each frame's row by its own
+ *   block in a fixed order.  Same envelope, same refusals; dF and dpart are bitwise those of
+ *   lbwn_lc_upsample_backward on the same inputs.
  * Every pointer is device memory, 16-byte aligned; F, act and dF are host arrays of nup device
  * pointers.  Outside the envelope both launches return EINVAL, naming the envelope, before any launch. */
 int lbwn_lc_upsample_fused_ok(int nup, const int* strides, int Li, int Lo);
@@ -665,6 +701,9 @@ int lbwn_lc_upsample_forward(int nup, const int* strides, int Li, int Lo, int fr
 int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
                               const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
                               int64_t dlc_stride, float* dpart, float* const* dF, void* stream);
+int lbwn_lc_upsample_backward_dmel(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                                   const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                                   int64_t dlc_stride, float* dpart, float* const* dF, float* dmel, void* stream);
 /* GC table and its gradients (tmodel.py:92-114, :150-154), with N = L·2·Cd and column
  * n = l·2Cd + s·Cd + o (s = 0 signal, 1 gate), emb [ncat1][Ge], wsig / wgate [L][Ge][Cd]:
  *   lbwn_gc_table: out[c][n] = Σ_e emb[c][e]·W_s[l][e][o], out [ncat1][N].

@@ -194,9 +194,12 @@ int lbwn_lc_upsample_forward(int nup, const int* strides, int Li, int Lo, int fr
   return lbwn_lc_up_fwd_launch(nup, strides, Li, Lo, frames, mel, F, act, (hipStream_t)stream);
 }
 
-int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
-                              const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
-                              int64_t dlc_stride, float* dpart, float* const* dF, void* stream) {
+}  // extern "C"
+
+// lbwn_lc_upsample_backward (dmel NULL) and lbwn_lc_upsample_backward_dmel: the same checks
+static int lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                                const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                                int64_t dlc_stride, float* dpart, float* const* dF, float* dmel, void* stream) {
   LBWN_REQUIRE(strides && mel && F && act && dlc && dpart && dF, "lc_upsample_backward: null argument");
   LBWN_REQUIRE(frames >= 1, "lc_upsample_backward: frames must be >= 1");
   LBWN_REQUIRE(lbwn_lc_up_fused_ok(nup, strides, Li, Lo),
@@ -216,10 +219,28 @@ int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int f
                "lc_upsample_backward: dlc_stride must be a multiple of 4 and >= frames*hop*Lo");
   LBWN_REQUIRE((((uintptr_t)dlc | (uintptr_t)mel | (uintptr_t)dpart) & 15) == 0,
                "lc_upsample_backward: mel, dlc and dpart must be 16-byte aligned");
+  LBWN_REQUIRE(((uintptr_t)dmel & 15) == 0, "lc_upsample_backward: dmel must be 16-byte aligned");
   float* a[4] = {nullptr, nullptr, nullptr, nullptr};   // read only by the backward
   for (int i = 0; i < nup; ++i) a[i] = const_cast<float*>(act[i]);
   return lbwn_lc_up_bwd_launch(nup, strides, Li, Lo, frames, mel, F, a, dlc, dpart, dF, (hipStream_t)stream, nullptr,
-                               nullptr, dlc_parts, (long)dlc_stride);
+                               nullptr, dlc_parts, (long)dlc_stride, dmel);
+}
+
+extern "C" {
+
+int lbwn_lc_upsample_backward(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                              const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                              int64_t dlc_stride, float* dpart, float* const* dF, void* stream) {
+  return lc_upsample_backward(nup, strides, Li, Lo, frames, mel, F, act, dlc, dlc_parts, dlc_stride, dpart, dF, nullptr,
+                              stream);
+}
+
+int lbwn_lc_upsample_backward_dmel(int nup, const int* strides, int Li, int Lo, int frames, const float* mel,
+                                   const float* const* F, const float* const* act, const float* dlc, int dlc_parts,
+                                   int64_t dlc_stride, float* dpart, float* const* dF, float* dmel, void* stream) {
+  LBWN_REQUIRE(dmel != nullptr, "lc_upsample_backward_dmel: dmel is null");
+  return lc_upsample_backward(nup, strides, Li, Lo, frames, mel, F, act, dlc, dlc_parts, dlc_stride, dpart, dF, dmel,
+                              stream);
 }
 
 int lbwn_gc_table(const float* emb, const float* wsig, const float* wgate, float* out, int L, int ncat1, int Ge, int Cd,

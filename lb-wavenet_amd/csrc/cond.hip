@@ -157,6 +157,7 @@ struct UpK {
   int dlc_parts; long dlc_stride;    // dlc_parts split-K partials dlc_stride floats apart (summed here)
   float* dpart;                      // backward: per-frame filter-gradient partials [frames][Σ_i s_i·Lo·I_i]
   int nup, s[4], Li, Lo, frames;
+  float* dmel;                       // backward<true>: d(mel) [frames][Li]
 };
 
 // F_i rows [n0, n0 + nr) (n = j·Lo + o, each I floats) -> W[n - n0][I + 4]
@@ -288,9 +289,12 @@ __global__ __launch_bounds__(UP_THREADS) void lc_up_fwd_kernel(UpK a) {
 
 // Backward, per frame, stages nup-1 .. 0 with D = d(stage output) rows [R·s][Lo] in LDS:
 //   dF_i partial [s·Lo][I] = Σ_t D[t][n]·IN[t][c]  (D viewed [R][s·Lo], IN = the stage input rows)
-//   din [R][I]             = Σ_n D[t][n]·F_i[n][c]  (the previous stage's D; skipped for stage 0)
+//   din [R][I]             = Σ_n D[t][n]·F_i[n][c]  (the previous stage's D; for stage 0 the mel
+//                            gradient: DMEL forms its one row in a loop of its own and stores it to
+//                            a.dmel, else it is skipped)
 // LDS = D [hop][Lo + 4] | DN (din) [hop / s_last][Lo + 4] | IN [R][I + 4] | W (one phase j of
 // F_i: [Lo][I + 4]), D and DN swapping roles per stage.
+template <bool DMEL>
 __global__ __launch_bounds__(UP_THREADS) void lc_up_bwd_kernel(UpK a) {
   __shared__ __attribute__((aligned(16))) float sm[UP_LDS];
   const int f = blockIdx.x, tid = threadIdx.x, Lo = a.Lo, LP = Lo + 4;
@@ -338,7 +342,38 @@ __global__ __launch_bounds__(UP_THREADS) void lc_up_bwd_kernel(UpK a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) *(floatx4*)(dp + (long)(4 * n4 + q) * I + 4 * c4) = acc[q];
     }
-    if (i == 0) break;   // no gradient into the mel input
+    if (i == 0) {   // no previous stage: the gradient into the mel input, when it is wanted
+      if (DMEL) {
+        // dmel row [Li] = Σ_{j,o} D[j][o]·F_0[j][o][c]: R = 1 input row, so the 2-row work items below
+        // would leave all but Li / 4 threads idle over K = s·Lo.  Here K is spread instead: thread
+        // (c4, sl) sums the o groups sl, sl + NS, ... of every phase j (F_0's phases through W as
+        // below), the NS slice sums go through W (free after the last phase: NS <= Lo / 4 rows of
+        // [Lo][I + 4]) and thread c4 adds them in slice order: a fixed order, the same bits every run.
+        const int G = Lo / 4, NS = min(G, UP_THREADS / C4), c4 = tid % C4, sl = tid / C4;
+        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < s; ++j) {
+          __syncthreads();   // W free
+          up_load_rows(W, a.F[0], j * Lo, Lo, I, tid);
+          __syncthreads();
+          if (sl < NS) {
+            for (int og = sl; og < G; og += NS) {
+              const floatx4 d0 = *(const floatx4*)(D + j * LP + 4 * og);
+#pragma unroll
+              for (int q = 0; q < 4; ++q) acc += d0[q] * *(const floatx4*)(W + (4 * og + q) * IP + 4 * c4);
+            }
+          }
+        }
+        __syncthreads();   // the last phase's readers are done with W
+        if (sl < NS) *(floatx4*)(W + sl * IP + 4 * c4) = acc;
+        __syncthreads();
+        if (tid < C4) {
+          floatx4 r = *(const floatx4*)(W + 4 * tid);
+          for (int z = 1; z < NS; ++z) r += *(const floatx4*)(W + z * IP + 4 * tid);
+          *(floatx4*)(a.dmel + (long)f * a.Li + 4 * tid) = r;
+        }
+      }
+      break;
+    }
     // din: work item = (2-row group, c4 group), K = s·Lo in phases j (one phase of F_i in W)
     const int RT2 = (R + 1) / 2, nwork = RT2 * C4;
     floatx4 acc[2][2];   // up to 2 work items per thread (R·I/8 <= 2·512)
@@ -453,12 +488,14 @@ int lbwn_lc_up_fwd_launch(int nup, const int* s, int Li, int Lo, int frames, con
 
 int lbwn_lc_up_bwd_launch(int nup, const int* s, int Li, int Lo, int frames, const float* mel, const float* const* F,
                           float* const* act, const float* dlc, float* dpart, float* const* dF, hipStream_t st,
-                          hipStream_t st_sum, hipEvent_t ev, int dlc_parts, long dlc_stride) {
+                          hipStream_t st_sum, hipEvent_t ev, int dlc_parts, long dlc_stride, float* dmel) {
   LBWN_REQUIRE(lbwn_lc_up_fused_ok(nup, s, Li, Lo), "lc upsample: shape outside the fused kernel's envelope");
   UpK k = up_args(nup, s, Li, Lo, frames, mel, F, act);
   k.dlc = dlc; k.dpart = dpart;
   k.dlc_parts = std::max(dlc_parts, 1); k.dlc_stride = dlc_stride;
-  lc_up_bwd_kernel<<<frames, UP_THREADS, 0, st>>>(k);
+  k.dmel = dmel;
+  if (dmel) lc_up_bwd_kernel<true><<<frames, UP_THREADS, 0, st>>>(k);    // ... and stage 0's din, to dmel
+  else lc_up_bwd_kernel<false><<<frames, UP_THREADS, 0, st>>>(k);
   LBWN_CHECK_LAUNCH();
   int ptot = 0;
   for (int i = 0; i < nup; ++i) ptot += s[i] * Lo * (i ? Lo : Li);

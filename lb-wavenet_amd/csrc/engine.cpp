@@ -69,6 +69,7 @@ struct lbwn_plan {
   const float* dlc_spl = nullptr;   // ... in this split-K workspace (checked by lc_upsample_bwd)
   bool up_fused_bwd = false;     // ... for the backward (<= 256 mel frames; else per-stage GEMMs)
   size_t oUPPART = 0;            // its per-frame filter-gradient partials
+  int dmel_fused = -1;           // the last backward that wrote dmel: 1 fused kernel, 0 GEMM; -1 none yet
   size_t total;
   long x_layer_stride;  // floats
   int split_post2, split_post1, split_skip;
@@ -574,6 +575,7 @@ int lbwn_plan_info(const lbwn_plan* p, const char* key, int64_t* value) {
     *value = p->split_up[key[8] - '0'];
   else if (!strcmp(key, "dv_blk")) *value = p->dv_blk;         // of the last backward
   else if (!strcmp(key, "dlc_parts")) *value = p->dlc_parts;   // of the last backward
+  else if (!strcmp(key, "dmel_fused")) *value = p->dmel_fused;   // of the last backward that wrote dmel
   else LBWN_REQUIRE(false, "plan_info: unknown key '%s'", key);
   return 0;
 }
@@ -805,10 +807,13 @@ int lc_dlc(lbwn_plan* p, const lbwn_params* P, void* ws, float* spl, hipStream_t
   return 0;
 }
 
+// dmel: nullable, the caller's [frames][Li] buffer for the gradient into the mel input (stage 0's
+// input gradient); without it both branches launch what they launched before it existed
 int lc_upsample_bwd(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, void* ws, const float* mel, float* spl,
-                    hipStream_t st, hipStream_t st_sum = nullptr) {
+                    float* dmel, hipStream_t st, hipStream_t st_sum = nullptr) {
   int e;
   const float* dout = at<float>(ws, p->oDLC[0]);
+  if (dmel) p->dmel_fused = p->up_fused_bwd ? 1 : 0;
   if (p->up_fused_bwd) {
     const float* F[8];
     float* act[8];
@@ -821,7 +826,7 @@ int lc_upsample_bwd(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, vo
     LBWN_REQUIRE(!parts || p->dlc_spl == spl, "lc upsample bwd: dlc's split-K partials are in another workspace");
     e = lbwn_lc_up_bwd_launch(p->nup, p->up, p->Li, p->Lo, (int)(p->M / p->hop), mel, F, act, parts ? spl : dout,
                               at<float>(ws, p->oUPPART), G->lc_up, st, st_sum, p->ev_upb, p->dlc_parts,
-                              parts ? p->M * p->Lo : 0);
+                              parts ? p->M * p->Lo : 0, dmel);
     Probe::end(p, st, "lc_up_bwd");
     return e;
   }
@@ -837,8 +842,10 @@ int lc_upsample_bwd(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, vo
     g.A = dout; g.lda = (long)s * p->Lo; g.B = in; g.ldb = I; g.C = G->lc_up[i]; g.ldc = I;
     g.M = s * p->Lo; g.N = I; g.K = (int)rows;
     if ((e = lbwn_gemm_launch(g, 0, 0, p->split_up[i], spl, st))) return e;
-    if (i == 0) break;  // no gradient into the mel input
-    float* din = at<float>(ws, p->oDLC[buf ^ 1]);
+    if (i == 0 && !dmel) break;  // no gradient into the mel input
+    // din[bt][i'] = Σ_(j,o) dout[bt][(j,o)] · F_i[(j,o)][i']; stage 0's is dmel, straight into the
+    // caller's buffer (with one stage dout is still the reduced dlc in oDLC[0])
+    float* din = i == 0 ? dmel : at<float>(ws, p->oDLC[buf ^ 1]);
     g = gemm0();
     g.A = dout; g.lda = (long)s * p->Lo; g.B = P->lc_up[i]; g.ldb = I; g.C = din; g.ldc = I;
     g.M = (int)rows; g.N = I; g.K = s * p->Lo;
@@ -1091,19 +1098,30 @@ int lbwn_train_eval(lbwn_plan* p, const lbwn_params* P, void* ws, const lbwn_eva
 // Backward (tmodel.py:338-340, TF autodiff of the graph above): head/skip GEMMs, then the
 // residual stack in reverse (one persistent chain launch, or one launch per layer), then
 // one batched reduction of every layer's weight-gradient partials, then dPRE.
-int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, void* ws, const int* wav_q,
-                        const int* ids, const float* mel, void* stream) {
-  LBWN_REQUIRE(p && P && G && ws && wav_q && ids, "train_backward: null argument");
+// dmel: nullable, fp32 [B][T/hop][n_lc_in]: the gradient into the mel input (lbwn_train_backward_ex);
+// NULL launches exactly what the backward launched before that output existed
+static int train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, void* ws, const int* wav_q,
+                          const int* ids, const float* mel, float* dmel, void* stream) {
+  LBWN_REQUIRE(p && P && G && ws && wav_q && ids, "train_backward: null argument (plan, params, grads, workspace, "
+                                                  "wav_q or ids)");
   LBWN_REQUIRE(p->Lo == 0 || mel, "train_backward: LC arch needs the mel input");
-  hipStream_t st = (hipStream_t)stream;
-  int e;
-  if ((e = ensure_device(p))) return e;
+  LBWN_REQUIRE(!dmel || p->Lo > 0, "train_backward: dmel on an arch without local conditioning");
+  LBWN_REQUIRE(!((uintptr_t)dmel & 15), "train_backward: dmel must be 16-byte aligned");
+  if (dmel) {   // written while mel and the workspace are still read
+    const uintptr_t d0 = (uintptr_t)dmel, nb = sizeof(float) * (size_t)(p->M / p->hop) * p->Li;
+    auto overlaps = [&](const void* q, size_t n) { return d0 < (uintptr_t)q + n && (uintptr_t)q < d0 + nb; };
+    LBWN_REQUIRE(!overlaps(mel, nb) && !overlaps(ws, p->total), "train_backward: dmel aliases mel or the workspace");
+  }
   // the backward consumes the forward's layout choices (SG rows, the head's column partials, dZ in
   // chain order), which follow the GEMM arithmetic: a mode switch in between would mix two paths
+  // (host checks: before the device is touched)
   LBWN_REQUIRE(p->fwd_mode >= 0, "train_backward: no training forward on this plan (lbwn_train_eval leaves none)");
   LBWN_REQUIRE(p->fwd_mode == lbwn_gemm_mode(),
                "train_backward: the GEMM mode changed since the forward (%d -> %d); run the forward again",
                p->fwd_mode, lbwn_gemm_mode());
+  hipStream_t st = (hipStream_t)stream;
+  int e;
+  if ((e = ensure_device(p))) return e;
   // padded head widths: the forward's padded images, gradients into padded buffers
   const lbwn_params* Gref = G;
   lbwn_params Ppad, Gpad;
@@ -1335,7 +1353,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     const bool lc_seq = p->Lo > 0 && (p->M + 255) / 256 * (long)p->split_dlcx > p->ncu;
     if (lc_seq) {   // dlc, the upsample backward and dLCcat first; the side stream then runs beside dSKIP
       if ((e = lc_dlc(p, P, ws, SPL, st))) return e;
-      if ((e = lc_upsample_bwd(p, P, G, ws, mel, SPL, st, st))) return e;
+      if ((e = lc_upsample_bwd(p, P, G, ws, mel, SPL, dmel, st, st))) return e;
       if ((e = lc_wgrad(p, G, ws, SPL, st))) return e;
       if (rst != st) {
         LBWN_HIP(hipEventRecord(p->ev_dlc, st));
@@ -1355,7 +1373,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     // main stream: dlc, the LC upsample backward (it needs dlc), [dLCcat,] then dSKIP below
     if (p->Lo > 0) {
       if (!lc_seq && (e = lc_dlc(p, P, ws, SPL, st))) return e;
-      if (!lc_seq && (e = lc_upsample_bwd(p, P, G, ws, mel, SPL, st, rst))) return e;   // its frame sum on the side
+      if (!lc_seq && (e = lc_upsample_bwd(p, P, G, ws, mel, SPL, dmel, st, rst))) return e;   // its frame sum on the side
     }
     if (p->aux2) {
       LBWN_HIP(hipEventRecord(p->ev_join2, rst));
@@ -1393,7 +1411,7 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
     if (p->Lo > 0) {
       if ((e = lc_wgrad(p, G, ws, SPL, st))) return e;
       if ((e = lc_dlc(p, P, ws, SPL, st))) return e;
-      if ((e = lc_upsample_bwd(p, P, G, ws, mel, SPL, st))) return e;
+      if ((e = lc_upsample_bwd(p, P, G, ws, mel, SPL, dmel, st))) return e;
     }
   }
   if ((e = dskip(st, SPL))) return e;
@@ -1405,4 +1423,18 @@ int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G
   if (p->chain && p->aux2) LBWN_HIP(hipStreamWaitEvent(st, p->ev_join2, 0));
   if ((e = head_unpad_grads(p, Gref, ws, st))) return e;
   return 0;
+}
+
+int lbwn_train_backward(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, void* ws, const int* wav_q,
+                        const int* ids, const float* mel, void* stream) {
+  return train_backward(p, P, G, ws, wav_q, ids, mel, nullptr, stream);
+}
+
+// ... with the optional outputs of lbwn_backward_args (dmel)
+int lbwn_train_backward_ex(lbwn_plan* p, const lbwn_params* P, const lbwn_params* G, void* ws,
+                           const lbwn_backward_args* a, void* stream) {
+  LBWN_REQUIRE(a != nullptr, "train_backward_ex: null argument struct (a)");
+  LBWN_REQUIRE(a->struct_size == sizeof(lbwn_backward_args),
+               "train_backward_ex: struct_size %zu != %zu (another ABI?)", a->struct_size, sizeof(lbwn_backward_args));
+  return train_backward(p, P, G, ws, a->wav_q, a->ids, a->mel, a->dmel, stream);
 }

@@ -323,11 +323,12 @@ int lbwn_lc_up_fused_ok(int nup, const int* s, int Li, int Lo);
 int lbwn_lc_up_part_floats(int nup, const int* s, int Li, int Lo, int frames);
 int lbwn_lc_up_fwd_launch(int nup, const int* s, int Li, int Lo, int frames, const float* mel, const float* const* F,
                           float* const* act, hipStream_t st);
-// the per-frame pass on st; the frame-partial sum on st_sum (after ev, recorded on st, when they differ)
+// the per-frame pass on st; the frame-partial sum on st_sum (after ev, recorded on st, when they differ);
+// dmel: nullable, d(mel) [frames][Li] (stage 0's input gradient, stored by the per-frame pass)
 int lbwn_lc_up_bwd_launch(int nup, const int* s, int Li, int Lo, int frames, const float* mel, const float* const* F,
                           float* const* act, const float* dlc, float* dpart, float* const* dF, hipStream_t st,
                           hipStream_t st_sum = nullptr, hipEvent_t ev = nullptr, int dlc_parts = 1,
-                          long dlc_stride = 0);
+                          long dlc_stride = 0, float* dmel = nullptr);
 
 // Log-mel front end (mel.hip).  The tables live in the caller's workspace:
 // basis [ncb][n_fft/4][2 (cos | sin)][32 bins][4 samples] f32 (windowed, zero past bin n_fft/2), then

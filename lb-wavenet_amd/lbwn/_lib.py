@@ -83,6 +83,15 @@ class EvalArgs(ctypes.Structure):
         self.struct_size = ctypes.sizeof(EvalArgs)
 
 
+class BackwardArgs(ctypes.Structure):
+    """lbwn_backward_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('wav_q', c_fp), ('ids', c_fp), ('mel', c_fp), ('dmel', c_fp)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(BackwardArgs)
+
+
 class MelCfg(ctypes.Structure):
     """lbwn_mel_cfg (include/lbwn.h), field for field; struct_size is set on construction."""
     _fields_ = [('struct_size', c_size_t), ('sample_rate', c_int), ('n_fft', c_int), ('win_length', c_int),
@@ -119,6 +128,8 @@ _SIGS = {
     'lbwn_train_forward': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_void_p]),
     'lbwn_train_backward': (c_int, [c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Params), c_fp, c_fp, c_fp,
                                     c_fp, c_void_p]),
+    'lbwn_train_backward_ex': (c_int, [c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Params), c_fp,
+                                       ctypes.POINTER(BackwardArgs), c_void_p]),
     'lbwn_train_eval_scratch_bytes': (c_size_t, [c_void_p, c_int]),
     'lbwn_train_eval': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(EvalArgs), c_void_p]),
     'lbwn_adam_tf1': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int64, c_int64, c_float, c_float, c_float, c_float,
@@ -168,6 +179,9 @@ _SIGS = {
     'lbwn_lc_upsample_backward': (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_fp,
                                           ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), c_fp, c_int, c_int64, c_fp,
                                           ctypes.POINTER(c_fp), c_void_p]),
+    'lbwn_lc_upsample_backward_dmel': (c_int, [c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_fp,
+                                               ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), c_fp, c_int, c_int64, c_fp,
+                                               ctypes.POINTER(c_fp), c_fp, c_void_p]),
     'lbwn_gc_table': (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_void_p]),
     'lbwn_gc_grads': (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_void_p]),
     'lbwn_gc_part_floats_abi': (c_int64, [c_int, c_int, c_int]),

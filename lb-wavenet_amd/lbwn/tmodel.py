@@ -77,6 +77,8 @@ class WaveNetTrain:
         self._ws = None
         self._last = None
         self._sp_cache = None
+        self._dmel = {}     # slice length -> the dmel buffer of forward(want_dmel=True)
+        self.dmel = None
         self.init_vars(seed)
         # host mirror of GLOBAL_STEP: counts the optimizer calls (attempted steps) so the print
         # cadence needs no sync; re-read from counters[0] by check_status, since a step skipped
@@ -179,10 +181,17 @@ class WaveNetTrain:
         self._plan(T)
         return self._plans[T][1]
 
-    def forward(self, wav_input, lc_input, id_mask, backward=True, stream=None):
+    def forward(self, wav_input, lc_input, id_mask, backward=True, stream=None, want_dmel=False):
         """Run the plan on one slice; wav_input int [B,T] mu-law codes (raw floats are
-        mu_encode'd first when wav_input_type == 'raw', tmodel.py:58-62)."""
+        mu_encode'd first when wav_input_type == 'raw', tmodel.py:58-62).  want_dmel: the backward
+        goes through lbwn_train_backward_ex and leaves in ``self.dmel`` the gradient of Σ masked xent
+        (a raw sum, like grad_flat) with respect to lc_input, a device tensor [B, T/hop, n_lc_in]: one
+        buffer per slice length, valid until the next forward."""
         dev = self.device
+        if want_dmel and not self.use_lc_input():
+            raise ValueError('want_dmel: this arch has no local conditioning (n_lc_out == 0)')
+        if want_dmel and not backward:
+            raise ValueError('want_dmel needs backward=True: dmel is an output of the backward')
         if self.wav_input_type == 'raw':
             from .ops import mu_encode
             wav_input = mu_encode(torch.as_tensor(wav_input, dtype=torch.float32, device=dev), self.n_quant)
@@ -200,7 +209,19 @@ class WaveNetTrain:
         _lib.check(self.lib.lbwn_train_forward(h, ctypes.byref(self._params_c), self._ws.data_ptr(), q.data_ptr(),
                                                ids.data_ptr(), _lib.ptr(mel), self.save_flat.data_ptr(),
                                                self.stats.data_ptr(), sp))
-        if backward:
+        self.dmel = None
+        if backward and want_dmel:
+            shape = (B, T // int(np.prod(self.lc_upsample)), self.n_lc_in)
+            if tuple(mel.shape) != shape:
+                raise ValueError('want_dmel: lc_input must be %s, got %s' % (shape, tuple(mel.shape)))
+            if T not in self._dmel:
+                self._dmel[T] = torch.empty(shape, dtype=torch.float32, device=dev)
+            self.dmel = self._dmel[T]
+            a = _lib.BackwardArgs(wav_q=q.data_ptr(), ids=ids.data_ptr(), mel=mel.data_ptr(),
+                                  dmel=self.dmel.data_ptr())
+            _lib.check(self.lib.lbwn_train_backward_ex(h, ctypes.byref(self._params_c), ctypes.byref(self._grads_c),
+                                                       self._ws.data_ptr(), ctypes.byref(a), sp))
+        elif backward:
             _lib.check(self.lib.lbwn_train_backward(h, ctypes.byref(self._params_c), ctypes.byref(self._grads_c),
                                                     self._ws.data_ptr(), q.data_ptr(), ids.data_ptr(),
                                                     _lib.ptr(mel), sp))

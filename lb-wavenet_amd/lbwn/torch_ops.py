@@ -4,6 +4,7 @@
 ``[x[t-d] | x[t]]``, tanh·σ gate, 1×1 residual): the HIP kernels behind ``lbwn_layer_forward``
 and ``lbwn_layer_backward``, composable with torch autograd so a caller can build its own stack
 (the training plan in ``tmodel.WaveNetTrain`` is the fused, fast path for whole networks).
+``wavenet_loss`` (at the end) is that whole plan as one function of its mel input under torch autograd.
 
 Layouts are the reference's (arch.py:112-167): ``w_sig``/``w_gate`` [2][n_res][n_dil] (tap 0
 = x[t-d]), ``w_res`` [n_dil][n_res], biases [n_dil] / [n_res].  ``x_halo`` is [B][H+T][n_res]
@@ -158,3 +159,47 @@ class DilatedResidualLayer(torch.nn.Module):
         with torch.no_grad():
             self.save.copy_(x_halo[:, H + T - d:H + T])
         return z, xo
+
+
+# ---- the whole network as one differentiable loss of its mel input -------------------
+
+class _WaveNetLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lc_input, net, wav_input, id_mask):
+        # forward + backward of the slice, eagerly: the engine's backward must follow its forward on
+        # the same workspace, so the gradient is formed here and only scaled in backward()
+        net.forward(wav_input, lc_input.detach(), id_mask, backward=True, want_dmel=True)
+        nv = net.stats[1]
+        den = torch.clamp(nv, min=1.0)
+        ctx.save_for_backward(net.dmel / den)      # a copy: net.dmel lives until the next forward
+        return torch.where(nv > 0, net.stats[0] / den, torch.zeros_like(nv))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        g, = ctx.saved_tensors
+        return grad_out * g, None, None, None
+
+
+def wavenet_loss(net, wav_input, lc_input, id_mask):
+    """Mean masked cross-entropy of one slice through ``net`` (a ``tmodel.WaveNetTrain`` with local
+    conditioning) as a 0-d tensor that is differentiable with respect to ``lc_input``
+    [B, T/hop, n_lc_in]: ``stats[0] / stats[1]`` (0 with nothing scored), its gradient
+    ``grad_out · net.dmel / n_valid`` formed on the device without a host synchronisation.  The slice
+    runs eagerly in the forward (lbwn_train_forward, then lbwn_train_backward_ex), so afterwards the
+    parameter gradients are in ``net.grad_flat`` exactly as after ``net.build()``, for the engine's own
+    Adam; a torch module that produced ``lc_input`` trains with any torch optimizer beside it.
+    ``wav_input`` and ``id_mask`` get no gradient.  Once-differentiable; device tensors only.  Refused
+    under an enabled DPContext: the mean there is over the global n_valid -- data-parallel callers take
+    the raw, rank-local ``net.dmel`` of ``net.forward(..., want_dmel=True)``, which needs no collective."""
+    if not net.use_lc_input():
+        raise ValueError('lbwn wavenet_loss: the arch has no local conditioning (n_lc_out == 0)')
+    if net.dp is not None and net.dp.enabled:
+        raise ValueError('lbwn wavenet_loss: not under data parallelism (the mean is over the global n_valid); '
+                         'use net.forward(..., want_dmel=True) and the raw net.dmel')
+    if not isinstance(lc_input, torch.Tensor) or lc_input.dtype != torch.float32:
+        raise ValueError('lbwn wavenet_loss: lc_input must be a float32 tensor')
+    if not lc_input.is_cuda or lc_input.device != net.flat.device:
+        raise ValueError('lbwn wavenet_loss: device tensors only: lc_input must be on the model device (%s)'
+                         % net.flat.device)
+    return _WaveNetLoss.apply(lc_input, net, wav_input, id_mask)
