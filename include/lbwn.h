@@ -118,6 +118,61 @@ int lbwn_recep_field_sz(const lbwn_arch* arch);
 int lbwn_train_forward(lbwn_plan* plan, const lbwn_params* params, void* workspace, const int* wav_q,
                        const int* ids, const float* mel, float* save, float* stats, void* stream);
 
+/* The training forward against a second distribution: knowledge distillation (soft targets at a
+ * temperature, mixed with the hard loss) and label smoothing (added after ABI 5 was declared, same ABI:
+ * symbols added, none altered).  The forward is lbwn_train_forward's up to the raw logits;
+ * the head then forms, per row m = (b, t), t < T-1, scored iff ids[b][t+1] != 0 with the target
+ * c = wav_q[b][t+1] (exactly as lbwn_train_forward), with l the student's logits of the row, u the
+ * teacher's, Q = n_quant, τ = distill_temp, α = distill_alpha, ε = label_smoothing:
+ *   p = softmax(l),  pS = softmax(l/τ),  pT = softmax(u/τ),  q_k = (1-ε)·[k == c] + ε/Q,
+ *   hard  = lse(l) - Σ_k q_k·l_k                    (lbwn_train_forward's xent when ε = 0)
+ *   kl    = Σ_k pT_k·(log pT_k - log pS_k)          (a term with pT_k = 0 contributes 0)
+ *   value = (1-α)·hard + α·τ²·kl
+ *   dlogits_k = (1-α)·(p_k - q_k) + α·τ·(pS_k - pT_k)
+ * dlogits are written in place over "logits", 0 at unscored rows and at t = T-1; the gradient is
+ * unnormalised and carries no l2 term, so lbwn_adam_* apply to it as they are.  The plan is left in the
+ * state lbwn_train_forward leaves: lbwn_train_backward and lbwn_train_backward_ex (dmel included) follow
+ * unchanged and give the gradients of Σ value.
+ *   stats     fp32[4] out: [0] Σ value (the quantity optimised), [1] n_valid, [2] Σ|argmax(l) - c|·mask,
+ *             [3] 1/n_valid (0 if none): [1..3] are lbwn_train_forward's.
+ *   stats_ex  nullable device fp32[4] out: [0] Σ plain, unsmoothed xent (comparable with lbwn_train_forward
+ *             and lbwn_train_eval), [1] Σ kl (not scaled by τ²), [2] = [3] = 0.
+ *   teacher_logits  device fp32, row m at teacher_logits + m·ld_teacher, n_quant values read; 16-byte
+ *             aligned, ld_teacher >= n_quant and a multiple of 4.  Rows of unscored positions and of
+ *             t = T-1 are not read; with α = 0 nothing is read and the pointer may be NULL.  The student's
+ *             logits are overwritten in place, so the teacher's must lie outside this plan's workspace:
+ *             another plan's workspace ("logits" after lbwn_train_eval) or a buffer of the caller's.
+ * All sums are formed in the head's fixed order (per wave in row order, ((w0+w1)+w2)+w3 per block, one
+ * fold); no floating-point atomics: two calls on the same inputs give the same bits.  The workspace size
+ * of every plan is what it was without this call.
+ * With α = 0 and ε = 0 (τ is then without effect, teacher_logits is not read) and stats_ex NULL the call
+ * launches exactly what lbwn_train_forward launches and gives its bits; with stats_ex the fold also writes
+ * stats_ex = (stats[0], 0, 0, 0), in the same number of launches.
+ * α, τ and ε are host scalars read at the call: a captured graph bakes them in (capture again to change
+ * them), as with lbwn_gen_set_sampling.
+ * EINVAL before any launch and before the device is touched, naming the argument: every refusal of
+ * lbwn_train_forward (a null plan, params, workspace, wav_q, ids, save or stats; mel NULL on an LC arch); a
+ * null args; struct_size != sizeof(lbwn_forward_args); distill_alpha outside [0, 1]; distill_temp not
+ * finite or <= 0; label_smoothing outside [0, 1); distill_alpha > 0 with teacher_logits NULL;
+ * teacher_logits not 16-byte aligned; ld_teacher < n_quant or not a multiple of 4; teacher_logits
+ * overlapping this plan's workspace. */
+typedef struct lbwn_forward_args {
+  size_t struct_size;
+  const int* wav_q;
+  const int* ids;
+  const float* mel;
+  float* save;
+  float* stats;
+  float* stats_ex;
+  const float* teacher_logits;
+  int64_t ld_teacher;
+  float distill_alpha;
+  float distill_temp;
+  float label_smoothing;
+} lbwn_forward_args;
+int lbwn_train_forward_ex(lbwn_plan* plan, const lbwn_params* params, void* workspace, const lbwn_forward_args* a,
+                          void* stream);
+
 /* Gradients of Σ masked xent (NOT divided by n_valid, no l2 term: both are applied in
  * lbwn_adam_tf1, so data-parallel ranks can all-reduce raw sums).  Replaces
  * compute_gradients (tmodel.py:354-358).  Must follow lbwn_train_forward on the same
@@ -757,6 +812,14 @@ int lbwn_dsep_save(const float* x_all, int64_t x_layer_stride, float* save, int 
  * partial_ws: 3·2048 floats. */
 int lbwn_head_xent(float* logits, const int* wav_q, const int* ids, int B, int T, int Q, int write_grad,
                    float* stats, float* partial_ws, void* stream);
+
+/* The head of lbwn_train_forward_ex alone (its objective, stats and stats_ex; no column partials):
+ * logits [B·T][Q] are overwritten with dlogits.  teacher: rows at teacher + m·ld_teacher, NULL allowed with
+ * alpha = 0.  stats_ex is nullable.  partial_ws: 5·2048 floats (the 3·2048 of lbwn_head_xent, then 2·2048
+ * for the plain xent and the KL).  alpha, temp and smoothing are host scalars read at the call. */
+int lbwn_head_xent_ex(float* logits, const int* wav_q, const int* ids, int B, int T, int Q, const float* teacher,
+                      int64_t ld_teacher, float alpha, float temp, float smoothing, float* stats, float* stats_ex,
+                      float* partial_ws, void* stream);
 
 #ifdef __cplusplus
 }

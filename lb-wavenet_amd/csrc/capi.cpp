@@ -361,4 +361,28 @@ int lbwn_head_xent(float* logits, const int* wav_q, const int* ids, int B, int T
   return lbwn_stats_reduce_launch(partial_ws, nb, stats, st);
 }
 
+int lbwn_head_xent_ex(float* logits, const int* wav_q, const int* ids, int B, int T, int Q, const float* teacher,
+                      int64_t ld_teacher, float alpha, float temp, float smoothing, float* stats, float* stats_ex,
+                      float* partial_ws, void* stream) {
+  LBWN_REQUIRE(logits && wav_q && ids && stats && partial_ws, "head_xent_ex: null argument");
+  LBWN_REQUIRE(T >= 2 && B >= 1 && Q >= 1, "head_xent_ex: B >= 1, slice_sz >= 2 and Q >= 1 required");
+  LBWN_REQUIRE(alpha >= 0.f && alpha <= 1.f, "head_xent_ex: alpha %g outside [0, 1]", (double)alpha);
+  LBWN_REQUIRE(std::isfinite(temp) && temp > 0.f, "head_xent_ex: temp %g must be finite and > 0", (double)temp);
+  LBWN_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "head_xent_ex: smoothing %g outside [0, 1)", (double)smoothing);
+  LBWN_REQUIRE(alpha == 0.f || teacher, "head_xent_ex: alpha > 0 needs the teacher's logits");
+  LBWN_REQUIRE(!teacher || ld_teacher >= Q, "head_xent_ex: ld_teacher %lld < Q %d", (long long)ld_teacher, Q);
+  lbwn_head_ex_args h;
+  h.logits = logits; h.q = wav_q; h.ids = ids; h.B = B; h.T = T; h.Q = Q;
+  h.teacher = alpha > 0.f ? teacher : nullptr;
+  h.ld_teacher = (long)ld_teacher;
+  h.alpha = alpha; h.temp = temp; h.inv_temp = 1.f / temp; h.eps = smoothing;
+  h.partial = partial_ws;
+  h.partial_ex = partial_ws + 3 * 2048;
+  h.colpart = nullptr;
+  int nb = 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = lbwn_head_ex_launch(h, &nb, st)) return e;
+  return lbwn_stats_reduce_ex_launch(h.partial, h.partial_ex, nb, stats, stats_ex, st);
+}
+
 }  // extern "C"

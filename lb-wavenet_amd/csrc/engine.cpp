@@ -1060,6 +1060,72 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
   return lbwn_stats_reduce_launch(h.partial, nb, stats, st);
 }
 
+// The training forward against a second distribution (include/lbwn.h): the forward
+// above, then the distilling / smoothing head.  Every argument check precedes the first device call.
+// With no option active the head and the launches are lbwn_train_forward's.
+int lbwn_train_forward_ex(lbwn_plan* p, const lbwn_params* P, void* ws, const lbwn_forward_args* a, void* stream) {
+  LBWN_REQUIRE(p, "train_forward_ex: plan is null");
+  LBWN_REQUIRE(P, "train_forward_ex: params is null");
+  LBWN_REQUIRE(ws, "train_forward_ex: workspace is null");
+  LBWN_REQUIRE(a, "train_forward_ex: args is null");
+  LBWN_REQUIRE(a->struct_size == sizeof(lbwn_forward_args), "train_forward_ex: struct_size %zu != %zu (another ABI?)",
+               a->struct_size, sizeof(lbwn_forward_args));
+  LBWN_REQUIRE(a->wav_q, "train_forward_ex: wav_q is null");
+  LBWN_REQUIRE(a->ids, "train_forward_ex: ids is null");
+  LBWN_REQUIRE(a->save, "train_forward_ex: save is null");
+  LBWN_REQUIRE(a->stats, "train_forward_ex: stats is null");
+  LBWN_REQUIRE(p->Lo == 0 || a->mel, "train_forward_ex: mel is null on an LC arch");
+  const float alpha = a->distill_alpha, temp = a->distill_temp, eps = a->label_smoothing;
+  LBWN_REQUIRE(alpha >= 0.f && alpha <= 1.f, "train_forward_ex: distill_alpha %g outside [0, 1]", (double)alpha);
+  LBWN_REQUIRE(std::isfinite(temp) && temp > 0.f, "train_forward_ex: distill_temp %g must be finite and > 0",
+               (double)temp);
+  LBWN_REQUIRE(eps >= 0.f && eps < 1.f, "train_forward_ex: label_smoothing %g outside [0, 1)", (double)eps);
+  LBWN_REQUIRE(alpha == 0.f || a->teacher_logits, "train_forward_ex: distill_alpha > 0 needs teacher_logits");
+  if (a->teacher_logits) {
+    LBWN_REQUIRE(!((uintptr_t)a->teacher_logits & 15), "train_forward_ex: teacher_logits must be 16-byte aligned");
+    LBWN_REQUIRE(a->ld_teacher >= p->Q && a->ld_teacher % 4 == 0,
+                 "train_forward_ex: ld_teacher %lld must be >= n_quant %d and a multiple of 4",
+                 (long long)a->ld_teacher, p->Q);
+    const uintptr_t t0 = (uintptr_t)a->teacher_logits, w0 = (uintptr_t)ws;
+    const size_t tb = sizeof(float) * ((size_t)(p->M - 1) * (size_t)a->ld_teacher + (size_t)p->Q);
+    LBWN_REQUIRE(!(t0 < w0 + p->total && w0 < t0 + tb),
+                 "train_forward_ex: teacher_logits overlaps this plan's workspace (the student's logits are "
+                 "overwritten in place: take the teacher's from another plan's workspace or a buffer of your own)");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int e;
+  if ((e = forward_to_logits(p, P, ws, a->wav_q, a->ids, a->mel, a->save, st))) return e;
+  const long M = p->M;
+  float* colpart = (lbwn_gemm_mode() == 1 && p->Q <= 512) ? at<float>(ws, p->oCOLS) : nullptr;
+  p->head_colparts = colpart ? lbwn_head_nblocks(M, true) : 0;
+  int nb = 0;
+  if (alpha == 0.f && eps == 0.f) {   // no option active: lbwn_train_forward's head
+    lbwn_head_args h;
+    h.logits = at<float>(ws, p->oLOG); h.q = a->wav_q; h.ids = a->ids; h.B = p->B; h.T = p->T; h.Q = p->Q;
+    h.partial = at<float>(ws, p->oHEADP); h.write_grad = 1;
+    h.colpart = colpart;
+    Probe(p, st, "head");
+    if ((e = lbwn_head_launch(h, &nb, st))) return e;
+    Probe::end(p, st, "head");
+    if (!a->stats_ex) return lbwn_stats_reduce_launch(h.partial, nb, a->stats, st);
+    return lbwn_stats_reduce_ex_launch(h.partial, nullptr, nb, a->stats, a->stats_ex, st);
+  }
+  lbwn_head_ex_args h;
+  h.logits = at<float>(ws, p->oLOG); h.q = a->wav_q; h.ids = a->ids; h.B = p->B; h.T = p->T; h.Q = p->Q;
+  h.teacher = alpha > 0.f ? a->teacher_logits : nullptr;   // alpha = 0: nothing of the teacher is read
+  h.ld_teacher = (long)a->ld_teacher;
+  h.alpha = alpha; h.temp = temp; h.inv_temp = 1.f / temp; h.eps = eps;
+  h.partial = at<float>(ws, p->oHEADP);
+  // the two further partials per block live in "dh", which the backward writes before it reads:
+  // at most 2·ceil(M/4) floats of its M·n_post (M >= 4), so no plan's workspace grows
+  h.partial_ex = at<float>(ws, p->oDH);
+  h.colpart = colpart;
+  Probe(p, st, "head");
+  if ((e = lbwn_head_ex_launch(h, &nb, st))) return e;
+  Probe::end(p, st, "head");
+  return lbwn_stats_reduce_ex_launch(h.partial, h.partial_ex, nb, a->stats, a->stats_ex, st);
+}
+
 // Held-out evaluation of one slice (include/lbwn.h): the forward above, then the evaluation head
 // over the raw logits.  Every argument check precedes the first device call.
 size_t lbwn_train_eval_scratch_bytes(const lbwn_plan* p, int n_bins) {

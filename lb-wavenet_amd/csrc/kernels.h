@@ -241,6 +241,26 @@ int lbwn_head_nblocks(long M, bool colpart);
 int lbwn_head_launch(const lbwn_head_args& a, int* nblocks_out, hipStream_t st);
 int lbwn_stats_reduce_launch(const float* partial, int nparts, float* stats, hipStream_t st);
 
+// The head against a second distribution (include/lbwn.h lbwn_train_forward_ex: distillation and
+// label smoothing; arguments checked by the caller).  The grid is lbwn_head_nblocks'.
+struct lbwn_head_ex_args {
+  float* logits;            // [M][Q] in: the student's logits, out: dlogits (unnormalised)
+  const int* q;             // [B][T] targets
+  const int* ids;           // [B][T]
+  int B, T, Q;
+  const float* teacher;     // [M][ld_teacher] the teacher's logits; NULL with alpha = 0 (never read)
+  long ld_teacher;
+  float alpha, temp, inv_temp, eps;
+  float* partial;           // [nblocks][3] (Σ value, n_valid, Σ |argmax diff|)
+  float* partial_ex;        // [nblocks][2] (Σ plain xent, Σ KL)
+  float* colpart;           // nullable: [nblocks][Q] column sums of the dlogits written (Q <= 512)
+};
+int lbwn_head_ex_launch(const lbwn_head_ex_args& a, int* nblocks_out, hipStream_t st);
+// stats as lbwn_stats_reduce_launch; stats_ex (nullable) = (Σ plain xent, Σ KL, 0, 0), or with
+// partial_ex NULL (after the plain head) (stats[0], 0, 0, 0)
+int lbwn_stats_reduce_ex_launch(const float* partial, const float* partial_ex, int nparts, float* stats,
+                                float* stats_ex, hipStream_t st);
+
 // lbwn_train_eval's head (misc.hip): the xent of the training head with no gradient written, per-block
 // partials in double, then a fixed-order fold into acc / by_voice
 struct lbwn_eval_head_args {

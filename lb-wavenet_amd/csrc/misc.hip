@@ -366,6 +366,324 @@ __global__ void stats_reduce_kernel(const float* partial, int nparts, float* sta
   }
 }
 
+// ---- distilling / label-smoothing head (lbwn_train_forward_ex) -------------------------
+// The objective of include/lbwn.h: per scored row, with l the student's logits, u the teacher's,
+//   value = (1-α)·(lse(l) - Σ q·l) + α·τ²·KL(softmax(u/τ) ‖ softmax(l/τ)),   q = (1-ε)·onehot + ε/Q,
+//   dlogits = (1-α)·(softmax(l) - q) + α·τ·(softmax(l/τ) - softmax(u/τ)),
+// written in place over the logits; 0 at unscored rows and at t = T-1.  The skeleton is the plain
+// head's: one wave per row, the register form in lane order c = lane + 64·j, the next row fetched
+// one row ahead.  The teacher's row is fetched only for a row that will be scored, so the ids run
+// two rows ahead of the row in hand: the id that decides whether row m + stride is scored has to be
+// in a register when that row's loads are issued.  a.teacher is NULL when α = 0: nothing of it is
+// read.  Block partials: partial [nb][3] (Σ value, count, Σ|argmax - c|) as the plain head, and
+// partial_ex [nb][2] (Σ plain xent, Σ KL), each ((w0+w1)+w2)+w3.
+struct head_ex_row {
+  float value, xent, kl;
+  int am;
+};
+
+// One scored row from registers.  v: the student's logits (-INF in padded lanes), u: the teacher's
+// (read only with TEACH); g: the gradient out (0 in padded lanes).
+template <int QV, bool TEACH>
+LBWN_DEV head_ex_row head_ex_row_reg(const lbwn_head_ex_args& a, const float (&v)[QV], const float (&u)[QV], int tgt,
+                                     int lane, float (&g)[QV]) {
+  const int Q = a.Q;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < QV; ++j) mx = fmaxf(mx, v[j]);
+  mx = wave_max(mx);
+  int am = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < QV; ++j)
+    if (am == 0x7fffffff && v[j] == mx) am = lane + 64 * j;
+  am = wave_min(am);
+  float e[QV], se = 0.f, pick = 0.f, sv = 0.f;
+#pragma unroll
+  for (int j = 0; j < QV; ++j) {
+    const bool in = lane + 64 * j < Q;
+    e[j] = in ? expf(v[j] - mx) : 0.f;
+    se += e[j];
+    sv += in ? v[j] : 0.f;
+    if (lane + 64 * j == tgt) pick = v[j];
+  }
+  se = wave_sum(se);
+  pick = wave_sum(pick);   // the one lane holding the target's logit; the rest add 0
+  const float lse = mx + logf(se);
+  head_ex_row r;
+  r.am = am;
+  r.xent = lse - pick;
+  r.kl = 0.f;
+  float hard = r.xent;
+  const float qoff = a.eps / (float)Q, qon = 1.f - a.eps;
+  if (a.eps != 0.f) {
+    sv = wave_sum(sv);
+    hard = lse - (qon * pick + qoff * sv);
+  }
+  const float inv = 1.f / se, wh = 1.f - a.alpha;
+#pragma unroll
+  for (int j = 0; j < QV; ++j) {
+    const int c = lane + 64 * j;
+    g[j] = c < Q ? wh * (e[j] * inv - ((c == tgt ? qon : 0.f) + qoff)) : 0.f;
+  }
+  if (TEACH) {
+    const float it = a.inv_temp;
+    float umx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < QV; ++j) umx = fmaxf(umx, u[j]);
+    umx = wave_max(umx);
+    // softmax(l/τ): the maximum of l/τ is mx/τ (τ > 0); at τ = 1 the exponentials above serve
+    const bool t1 = a.temp == 1.f;
+    float es[QV], et[QV], ses = 0.f, set = 0.f;
+#pragma unroll
+    for (int j = 0; j < QV; ++j) {
+      const bool in = lane + 64 * j < Q;
+      es[j] = t1 ? e[j] : (in ? expf((v[j] - mx) * it) : 0.f);
+      et[j] = in ? expf((u[j] - umx) * it) : 0.f;
+      ses += es[j];
+      set += et[j];
+    }
+    ses = t1 ? se : wave_sum(ses);
+    set = wave_sum(set);
+    const float ls = logf(ses), lt = logf(set), is = 1.f / ses, itt = 1.f / set, wt = a.alpha * a.temp;
+    float kl = 0.f;
+#pragma unroll
+    for (int j = 0; j < QV; ++j) {
+      const float ps = es[j] * is, pt = et[j] * itt;
+      // a padded lane (-INF in both rows) and a code whose teacher probability underflowed have
+      // et = 0 and add exactly 0, never (-INF) - (-INF)
+      if (et[j] > 0.f) kl += pt * (((u[j] - umx) * it - lt) - ((v[j] - mx) * it - ls));
+      g[j] += wt * (ps - pt);   // padded lanes: 0 - 0
+    }
+    r.kl = wave_sum(kl);
+  }
+  r.value = wh * hard + a.alpha * (a.temp * a.temp) * r.kl;
+  return r;
+}
+
+template <int QV, bool TEACH>
+__global__ __launch_bounds__(256) void head_ex_reg_kernel(lbwn_head_ex_args a) {
+  __shared__ float part[4][5];
+  __shared__ float cpart[4][64 * QV];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long M = (long)a.B * a.T;
+  const int Q = a.Q, T = a.T;
+  float s_val = 0.f, s_valid = 0.f, s_diff = 0.f, s_xent = 0.f, s_kl = 0.f;
+  float cs[QV];
+#pragma unroll
+  for (int j = 0; j < QV; ++j) cs[j] = 0.f;
+  const long stride = (long)gridDim.x * 4;
+  long m = (long)blockIdx.x * 4 + w;
+  // (student row, teacher row, target, id) of the row in hand's successor; the id of the row after
+  auto scored_at = [&](long r, int id) { return r < M && (int)(r % T) != T - 1 && id != 0; };
+  float vn[QV], un[QV];
+  int tn = 0, idn = 0, idnn = 0;
+  {
+    const long mc = min(m, M - 1), mq = min(mc + 1, M - 1);
+#pragma unroll
+    for (int j = 0; j < QV; ++j) vn[j] = a.logits[mc * Q + min(lane + 64 * j, Q - 1)];
+    tn = a.q[mq];
+    idn = a.ids[mq];
+    idnn = a.ids[min(min(m + stride, M - 1) + 1, M - 1)];
+#pragma unroll
+    for (int j = 0; j < QV; ++j) un[j] = 0.f;
+    if (TEACH && scored_at(m, idn)) {   // wave-uniform
+#pragma unroll
+      for (int j = 0; j < QV; ++j) un[j] = a.teacher[m * a.ld_teacher + min(lane + 64 * j, Q - 1)];
+    }
+  }
+  for (; m < M; m += stride) {
+    float* row = a.logits + m * Q;
+    float v[QV], u[QV];
+#pragma unroll
+    for (int j = 0; j < QV; ++j) {
+      v[j] = (lane + 64 * j < Q) ? vn[j] : -INFINITY;
+      u[j] = (lane + 64 * j < Q) ? un[j] : -INFINITY;
+    }
+    const int tgt = tn;
+    const bool scored = scored_at(m, idn);
+    {
+      const long m1 = m + stride, mc = min(m1, M - 1), mq = min(mc + 1, M - 1);
+#pragma unroll
+      for (int j = 0; j < QV; ++j) vn[j] = a.logits[mc * Q + min(lane + 64 * j, Q - 1)];
+      tn = a.q[mq];
+      idn = idnn;
+      idnn = a.ids[min(min(m1 + stride, M - 1) + 1, M - 1)];
+      if (TEACH && scored_at(m1, idn)) {
+#pragma unroll
+        for (int j = 0; j < QV; ++j) un[j] = a.teacher[m1 * a.ld_teacher + min(lane + 64 * j, Q - 1)];
+      }
+    }
+    if (!scored) {   // t = T-1 (no target, tmodel.py:231) or a masked target (tmodel.py:232): dlogits = 0
+#pragma unroll
+      for (int j = 0; j < QV; ++j)
+        if (lane + 64 * j < Q) row[lane + 64 * j] = 0.f;
+      continue;
+    }
+    float g[QV];
+    const head_ex_row r = head_ex_row_reg<QV, TEACH>(a, v, u, tgt, lane, g);
+#pragma unroll
+    for (int j = 0; j < QV; ++j) {
+      if (lane + 64 * j < Q) row[lane + 64 * j] = g[j];
+      cs[j] += g[j];
+    }
+    if (lane == 0) {
+      s_val += r.value;
+      s_valid += 1.f;
+      s_diff += fabsf((float)(tgt - r.am));
+      s_xent += r.xent;
+      s_kl += r.kl;
+    }
+  }
+  if (lane == 0) {
+    part[w][0] = s_val;
+    part[w][1] = s_valid;
+    part[w][2] = s_diff;
+    part[w][3] = s_xent;
+    part[w][4] = s_kl;
+  }
+  if (a.colpart) {
+#pragma unroll
+    for (int j = 0; j < QV; ++j) cpart[w][lane + 64 * j] = cs[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const int k = threadIdx.x;
+    const float s = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+    if (k < 3) a.partial[blockIdx.x * 3 + k] = s;
+    else a.partial_ex[blockIdx.x * 2 + (k - 3)] = s;
+  }
+  if (a.colpart)
+    for (int c = threadIdx.x; c < Q; c += 256)
+      a.colpart[(long)blockIdx.x * Q + c] = ((cpart[0][c] + cpart[1][c]) + cpart[2][c]) + cpart[3][c];
+}
+
+// Any width (Q > 512): the rows are walked in memory, three passes (maxima; sums; gradient and KL).
+template <bool TEACH>
+__global__ __launch_bounds__(256) void head_ex_kernel(lbwn_head_ex_args a) {
+  __shared__ float part[4][5];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long M = (long)a.B * a.T;
+  const int Q = a.Q;
+  float s_val = 0.f, s_valid = 0.f, s_diff = 0.f, s_xent = 0.f, s_kl = 0.f;
+  for (long m = (long)blockIdx.x * 4 + w; m < M; m += (long)gridDim.x * 4) {
+    float* row = a.logits + m * Q;
+    const int t = (int)(m % a.T);
+    const bool scored = t != a.T - 1 && a.ids[min(m + 1, M - 1)] != 0;
+    if (!scored) {
+      for (int c = lane; c < Q; c += 64) row[c] = 0.f;
+      continue;
+    }
+    const int tgt = a.q[m + 1];
+    const float* trow = TEACH ? a.teacher + m * a.ld_teacher : nullptr;
+    float mx = -INFINITY, umx = -INFINITY;
+    for (int c = lane; c < Q; c += 64) {
+      mx = fmaxf(mx, row[c]);
+      if (TEACH) umx = fmaxf(umx, trow[c]);
+    }
+    mx = wave_max(mx);
+    if (TEACH) umx = wave_max(umx);
+    const bool t1 = a.temp == 1.f;
+    const float it = a.inv_temp;
+    int am = 0x7fffffff;
+    float se = 0.f, pick = 0.f, sv = 0.f, ses = 0.f, set = 0.f;
+    for (int c = lane; c < Q; c += 64) {
+      const float x = row[c];
+      if (am == 0x7fffffff && x == mx) am = c;
+      se += expf(x - mx);
+      sv += x;
+      if (c == tgt) pick = x;
+      if (TEACH) {
+        if (!t1) ses += expf((x - mx) * it);
+        set += expf((trow[c] - umx) * it);
+      }
+    }
+    am = wave_min(am);
+    se = wave_sum(se);
+    pick = wave_sum(pick);
+    const float lse = mx + logf(se);
+    const float xent = lse - pick;
+    float hard = xent;
+    const float qoff = a.eps / (float)Q, qon = 1.f - a.eps;
+    if (a.eps != 0.f) {
+      sv = wave_sum(sv);
+      hard = lse - (qon * pick + qoff * sv);
+    }
+    float ls = 0.f, lt = 0.f, is = 0.f, itt = 0.f;
+    if (TEACH) {
+      ses = t1 ? se : wave_sum(ses);
+      set = wave_sum(set);
+      ls = logf(ses); lt = logf(set); is = 1.f / ses; itt = 1.f / set;
+    }
+    const float inv = 1.f / se, wh = 1.f - a.alpha, wt = a.alpha * a.temp;
+    float kl = 0.f;
+    for (int c = lane; c < Q; c += 64) {
+      const float x = row[c];
+      float g = wh != 0.f ? wh * (expf(x - mx) * inv - ((c == tgt ? qon : 0.f) + qoff)) : 0.f;
+      if (TEACH) {
+        const float ds = (x - mx) * it, dt = (trow[c] - umx) * it;
+        const float es = expf(ds), et = expf(dt);
+        if (et > 0.f) kl += (et * itt) * ((dt - lt) - (ds - ls));
+        g += wt * (es * is - et * itt);
+      }
+      row[c] = g;
+    }
+    if (TEACH) kl = wave_sum(kl);
+    if (lane == 0) {
+      s_val += wh * hard + a.alpha * (a.temp * a.temp) * kl;
+      s_valid += 1.f;
+      s_diff += fabsf((float)(tgt - am));
+      s_xent += xent;
+      s_kl += kl;
+    }
+  }
+  if (lane == 0) {
+    part[w][0] = s_val;
+    part[w][1] = s_valid;
+    part[w][2] = s_diff;
+    part[w][3] = s_xent;
+    part[w][4] = s_kl;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const int k = threadIdx.x;
+    const float s = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+    if (k < 3) a.partial[blockIdx.x * 3 + k] = s;
+    else a.partial_ex[blockIdx.x * 2 + (k - 3)] = s;
+  }
+}
+
+// stats as stats_reduce_kernel (the same sums in the same order), and stats_ex[0] = Σ plain xent,
+// [1] = Σ KL, [2] = [3] = 0.  partial_ex NULL (the plain head ran): stats_ex[0] = stats[0], [1] = 0.
+__global__ void stats_reduce_ex_kernel(const float* partial, const float* partial_ex, int nparts, float* stats,
+                                       float* stats_ex) {
+  __shared__ double sh[5][256];
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int p = threadIdx.x; p < nparts; p += blockDim.x) {
+    for (int k = 0; k < 3; ++k) s[k] += partial[p * 3 + k];
+    if (partial_ex)
+      for (int k = 0; k < 2; ++k) s[3 + k] += partial_ex[p * 2 + k];
+  }
+  for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st)
+      for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[0] = (float)sh[0][0];
+    stats[1] = (float)sh[1][0];
+    stats[2] = (float)sh[2][0];
+    stats[3] = sh[1][0] > 0 ? (float)(1.0 / sh[1][0]) : 0.f;
+    if (stats_ex) {
+      stats_ex[0] = (float)(partial_ex ? sh[3][0] : sh[0][0]);
+      stats_ex[1] = (float)sh[4][0];
+      stats_ex[2] = 0.f;
+      stats_ex[3] = 0.f;
+    }
+  }
+}
+
 // ---- evaluation head (lbwn_train_eval) -----------------------------------------------------------
 // The training head's xent without its gradient: the logits are read and never written.  One wave
 // per row, the row in registers for QV > 0 (Q <= 64·QV, head_reg_kernel's lane order c = lane +
@@ -933,6 +1251,34 @@ int lbwn_head_nblocks(long M, bool colpart) {
 
 int lbwn_stats_reduce_launch(const float* partial, int nparts, float* stats, hipStream_t st) {
   stats_reduce_kernel<<<1, 256, 0, st>>>(partial, nparts, stats);
+  LBWN_CHECK_LAUNCH();
+  return 0;
+}
+
+// the distilling / smoothing head: the plain head's grid; a.teacher NULL (α = 0) selects the forms
+// that read no teacher
+int lbwn_head_ex_launch(const lbwn_head_ex_args& a, int* nblocks_out, hipStream_t st) {
+  const long M = (long)a.B * a.T;
+  LBWN_REQUIRE(!a.colpart || a.Q <= 512, "head_ex: column partials need Q <= 512");
+  LBWN_REQUIRE(a.teacher || a.alpha == 0.f, "head_ex: alpha > 0 needs the teacher's logits");
+  const int nb = lbwn_head_nblocks(M, a.colpart != nullptr);
+  if (a.teacher) {
+    if (a.Q <= 256) head_ex_reg_kernel<4, true><<<nb, 256, 0, st>>>(a);
+    else if (a.Q <= 512) head_ex_reg_kernel<8, true><<<nb, 256, 0, st>>>(a);
+    else head_ex_kernel<true><<<nb, 256, 0, st>>>(a);
+  } else {
+    if (a.Q <= 256) head_ex_reg_kernel<4, false><<<nb, 256, 0, st>>>(a);
+    else if (a.Q <= 512) head_ex_reg_kernel<8, false><<<nb, 256, 0, st>>>(a);
+    else head_ex_kernel<false><<<nb, 256, 0, st>>>(a);
+  }
+  LBWN_CHECK_LAUNCH();
+  if (nblocks_out) *nblocks_out = nb;
+  return 0;
+}
+
+int lbwn_stats_reduce_ex_launch(const float* partial, const float* partial_ex, int nparts, float* stats,
+                                float* stats_ex, hipStream_t st) {
+  stats_reduce_ex_kernel<<<1, 256, 0, st>>>(partial, partial_ex, nparts, stats, stats_ex);
   LBWN_CHECK_LAUNCH();
   return 0;
 }

@@ -92,6 +92,17 @@ class BackwardArgs(ctypes.Structure):
         self.struct_size = ctypes.sizeof(BackwardArgs)
 
 
+class ForwardArgs(ctypes.Structure):
+    """lbwn_forward_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('wav_q', c_fp), ('ids', c_fp), ('mel', c_fp), ('save', c_fp),
+                ('stats', c_fp), ('stats_ex', c_fp), ('teacher_logits', c_fp), ('ld_teacher', c_int64),
+                ('distill_alpha', c_float), ('distill_temp', c_float), ('label_smoothing', c_float)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(ForwardArgs)
+
+
 class MelCfg(ctypes.Structure):
     """lbwn_mel_cfg (include/lbwn.h), field for field; struct_size is set on construction."""
     _fields_ = [('struct_size', c_size_t), ('sample_rate', c_int), ('n_fft', c_int), ('win_length', c_int),
@@ -126,6 +137,7 @@ _SIGS = {
     'lbwn_plan_stream_wait': (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int)]),
     'lbwn_plan_tensor': (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     'lbwn_train_forward': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_void_p]),
+    'lbwn_train_forward_ex': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(ForwardArgs), c_void_p]),
     'lbwn_train_backward': (c_int, [c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Params), c_fp, c_fp, c_fp,
                                     c_fp, c_void_p]),
     'lbwn_train_backward_ex': (c_int, [c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Params), c_fp,
@@ -197,6 +209,8 @@ _SIGS = {
     'lbwn_dsep_prepend': (c_int, [c_fp, c_int64, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'lbwn_dsep_save': (c_int, [c_fp, c_int64, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'lbwn_head_xent': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_void_p]),
+    'lbwn_head_xent_ex': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_int64, c_float, c_float, c_float,
+                                  c_fp, c_fp, c_fp, c_void_p]),
 }
 
 EXPORTED = sorted(_SIGS)

@@ -9,6 +9,7 @@ HIP launches on the current torch stream.  The reference's TF-eager flow (train.
 
 is reproduced literally (lbwn.optim.AdamOptimizer).
 """
+import contextlib
 import ctypes
 import sys
 from collections import OrderedDict
@@ -79,6 +80,10 @@ class WaveNetTrain:
         self._sp_cache = None
         self._dmel = {}     # slice length -> the dmel buffer of forward(want_dmel=True)
         self.dmel = None
+        self._stats_ex = None   # allocated by the first forward with distillation or label smoothing
+        self.stats_ex = None
+        self._local_nv = None
+        self._teacher = None
         self.init_vars(seed)
         # host mirror of GLOBAL_STEP: counts the optimizer calls (attempted steps) so the print
         # cadence needs no sync; re-read from counters[0] by check_status, since a step skipped
@@ -181,13 +186,37 @@ class WaveNetTrain:
         self._plan(T)
         return self._plans[T][1]
 
-    def forward(self, wav_input, lc_input, id_mask, backward=True, stream=None, want_dmel=False):
+    def logits_view(self, T):
+        """Torch view [B·T, n_quant] of the plan's "logits" at slice length T: the raw logits after
+        ``eval_slice``, the dlogits after ``forward``.  A view of the workspace: valid until the plan's
+        next call on it."""
+        return self.plan_tensor(T, 'logits').view(self.batch_sz * T, self.n_quant)
+
+    def forward(self, wav_input, lc_input, id_mask, backward=True, stream=None, want_dmel=False,
+                teacher_logits=None, distill_alpha=0.0, distill_temp=1.0, label_smoothing=0.0):
         """Run the plan on one slice; wav_input int [B,T] mu-law codes (raw floats are
         mu_encode'd first when wav_input_type == 'raw', tmodel.py:58-62).  want_dmel: the backward
         goes through lbwn_train_backward_ex and leaves in ``self.dmel`` the gradient of Σ masked xent
         (a raw sum, like grad_flat) with respect to lc_input, a device tensor [B, T/hop, n_lc_in]: one
-        buffer per slice length, valid until the next forward."""
+        buffer per slice length, valid until the next forward.
+
+        Distillation and label smoothing (lbwn_train_forward_ex): ``teacher_logits`` is a
+        device fp32 tensor [B·T, >= n_quant] or [B, T, n_quant] whose row stride becomes ld_teacher
+        (it must not be this net's own workspace), ``distill_alpha`` the weight of the soft term,
+        ``distill_temp`` its temperature, ``label_smoothing`` ε.  stats[0] is then Σ of the objective,
+        and ``self.stats_ex`` a device fp32[4]: (Σ plain xent, Σ KL, 0, 0), rank-local under data
+        parallelism.  With distill_alpha == 0 and label_smoothing == 0 the call is
+        lbwn_train_forward's and ``self.stats_ex`` is None: stats[0] is the plain xent."""
         dev = self.device
+        alpha, temp, eps = float(distill_alpha), float(distill_temp), float(label_smoothing)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError('distill_alpha %r outside [0, 1]' % (distill_alpha,))
+        if not (np.isfinite(temp) and temp > 0.0):
+            raise ValueError('distill_temp %r must be finite and > 0' % (distill_temp,))
+        if not 0.0 <= eps < 1.0:
+            raise ValueError('label_smoothing %r outside [0, 1)' % (label_smoothing,))
+        if alpha > 0.0 and teacher_logits is None:
+            raise ValueError('distill_alpha > 0 needs teacher_logits')
         if want_dmel and not self.use_lc_input():
             raise ValueError('want_dmel: this arch has no local conditioning (n_lc_out == 0)')
         if want_dmel and not backward:
@@ -206,9 +235,42 @@ class WaveNetTrain:
         h = self._plan(T)
         sp = _lib.stream_ptr(stream)
         self._last = (q, ids, mel)   # keep inputs alive until the stream consumed them
-        _lib.check(self.lib.lbwn_train_forward(h, ctypes.byref(self._params_c), self._ws.data_ptr(), q.data_ptr(),
-                                               ids.data_ptr(), _lib.ptr(mel), self.save_flat.data_ptr(),
-                                               self.stats.data_ptr(), sp))
+        self._teacher = None
+        if alpha == 0.0 and eps == 0.0:
+            self.stats_ex = None
+            _lib.check(self.lib.lbwn_train_forward(h, ctypes.byref(self._params_c), self._ws.data_ptr(), q.data_ptr(),
+                                                   ids.data_ptr(), _lib.ptr(mel), self.save_flat.data_ptr(),
+                                                   self.stats.data_ptr(), sp))
+        else:
+            tl, ld = None, 0
+            if alpha > 0.0:
+                tl = teacher_logits
+                if not (isinstance(tl, torch.Tensor) and tl.dtype == torch.float32 and tl.device == self.flat.device):
+                    raise ValueError('teacher_logits must be an fp32 tensor on the model device')
+                if tl.dim() == 3:
+                    if tuple(tl.shape) != (B, T, self.n_quant) or not tl.is_contiguous():
+                        raise ValueError('teacher_logits [B, T, Q] must be contiguous %s, got %s'
+                                         % ((B, T, self.n_quant), tuple(tl.shape)))
+                    tl = tl.view(B * T, self.n_quant)
+                if tl.dim() != 2 or tl.shape[0] != B * T or tl.shape[1] < self.n_quant or tl.stride(1) != 1:
+                    raise ValueError('teacher_logits must be [B·T, >= n_quant] with unit column stride, got %s'
+                                     % (tuple(tl.shape),))
+                ld = tl.stride(0)
+            if self._stats_ex is None:
+                self._stats_ex = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.stats_ex = self._stats_ex
+            self._teacher = tl          # kept alive with the inputs; None: label smoothing alone
+            a = _lib.ForwardArgs(wav_q=q.data_ptr(), ids=ids.data_ptr(), mel=_lib.ptr(mel),
+                                 save=self.save_flat.data_ptr(), stats=self.stats.data_ptr(),
+                                 stats_ex=self.stats_ex.data_ptr(), teacher_logits=_lib.ptr(tl), ld_teacher=ld,
+                                 distill_alpha=alpha, distill_temp=temp, label_smoothing=eps)
+            _lib.check(self.lib.lbwn_train_forward_ex(h, ctypes.byref(self._params_c), self._ws.data_ptr(),
+                                                      ctypes.byref(a), sp))
+            # this rank's own count beside its own stats_ex (stats[1] is summed over ranks later)
+            self._local_nv = None
+            if self.dp is not None and self.dp.enabled:
+                with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                    self._local_nv = self.stats[1].clone()
         self.dmel = None
         if backward and want_dmel:
             shape = (B, T // int(np.prod(self.lc_upsample)), self.n_lc_in)
@@ -375,8 +437,15 @@ class WaveNetTrain:
         world = self.dp.world if self.dp is not None else 1     # stats[2] is summed over ranks
         avg_diff = int(st[2]) // (world * B * (T - 1))
         pct = cnt[1] * 100.0 / self.n_valid_total if self.n_valid_total else 0.0
-        return ('{:5d}\t{:8.4f}\t{:8.4f}\t{:7.2f}\t{:5.0f}\t{:5.0f}\t{:10d}\t{:14d}\t{:5.2f}'.format(
+        line = ('{:5d}\t{:8.4f}\t{:8.4f}\t{:7.2f}\t{:5.0f}\t{:5.0f}\t{:10d}\t{:14d}\t{:5.2f}'.format(
             cnt[0], total, mean, l2, avg_diff, nv, cnt[1], int(self.n_valid_total), pct))
+        if self.stats_ex is not None and self._teacher is not None:
+            # distilling: total and mean above are the objective; the plain xent and the KL follow
+            # (this rank's own sums over this rank's own count: stats_ex is not reduced)
+            ex = self.stats_ex.tolist()
+            nloc = int(self._local_nv.item()) if self._local_nv is not None else nv
+            line += '\t{:8.4f}\t{:8.4f}'.format(ex[0] / nloc if nloc else 0.0, ex[1] / nloc if nloc else 0.0)
+        return line
 
     def maybe_print(self, file=None):
         """The in-graph progress print (tmodel.py:272-281): every print_interval steps,
@@ -386,8 +455,9 @@ class WaveNetTrain:
             print(self.progress_line(), file=file or sys.stderr)
 
     # ---- checkpoints (ckpt.py:53-81) --------------------------------------------------------
-    def save(self, step, optimizer=None):
-        """Write '<ckpt_path>-<step>.safetensors'; with ``optimizer`` its Adam slots too.
+    def save(self, step, optimizer=None, more=None):
+        """Write '<ckpt_path>-<step>.safetensors'; with ``optimizer`` its Adam slots too, and the
+        tensors of ``more`` (e.g. Distiller.state_tensors()) as they are.
         Data-parallel: a collective (every rank calls it).  The weights are replicated, but
         SAVE is per stream, so the ranks' rows are gathered and rank 0 writes the SAVE of
         the GLOBAL batch [world·B, d, Cr] -- the same file a single process over world·B
@@ -395,6 +465,8 @@ class WaveNetTrain:
         if self.device.type == 'cuda':
             torch.cuda.synchronize(self.device)
         extra = dict(optimizer.state_tensors(self)) if optimizer is not None else {}
+        if more:
+            extra.update(more)
         if self.dp is not None and self.dp.enabled:
             extra.update(self._gather_save())
             if self.dp.rank != 0:

@@ -25,6 +25,16 @@ stderr and appends it to <CKPT_PATH_PFX>.valid.tsv; --valid-ema adds a `valid_em
 shadows.  --eval-only (with --resume-step) restores, evaluates, prints and returns without a training
 step.  PAR_FILE keys: valid_file, valid_interval, valid_batches, valid_ema.
 
+Distillation and label smoothing (build extension, lbwn_train_forward_ex): --teacher-arch JSON
+--teacher-ckpt PATH [--teacher-ema] load a second net whose logits of every slice are the soft targets;
+--distill-alpha (default 0.5 with a teacher) weighs the soft term, --distill-temp (default 1) is its
+temperature, --label-smoothing smooths the hard targets (with or without a teacher).  The dataset's
+receptive field is then the larger of the two nets', checkpoints carry the teacher's lookback under
+TEACHER/<save var>, and the progress line's total and mean are the objective that is optimised; with a
+teacher two columns follow the existing ones: the plain xent and the KL (means over this rank's scored
+positions).  --valid-file still reports the hard xent.  PAR_FILE keys: teacher_arch, teacher_ckpt,
+teacher_ema, distill_alpha, distill_temp, label_smoothing.
+
 TF-only switches are accepted for command-line compatibility: --tf-eager is implied,
 --add-summary/--tb-dir/--prof-dir/--timeline-file print what replaces them (rocprofv3),
 --tf-debug and --cpu-only exit(1) (there is no CPU execution path).
@@ -91,6 +101,18 @@ def get_args(argv=None):
                    help='(build extension) also evaluate the EMA shadows (needs --ema-decay)')
     p.add_argument('--eval-only', action='store_true', default=False,
                    help='(build extension) restore --resume-step, evaluate --valid-file, print and exit')
+    p.add_argument('--teacher-arch', type=str, metavar='JSON',
+                   help='(build extension) ARCH_FILE of a teacher net to distil from (needs --teacher-ckpt)')
+    p.add_argument('--teacher-ckpt', type=str, metavar='PATH',
+                   help='(build extension) the teacher\'s checkpoint: a .safetensors file or a <pfx>-<step> prefix')
+    p.add_argument('--teacher-ema', action='store_true', default=None,
+                   help='(build extension) take the teacher\'s EMA shadows from the checkpoint')
+    p.add_argument('--distill-alpha', type=float, metavar='FLOAT',
+                   help='(build extension) weight of the soft term, in [0, 1] (default 0.5 with a teacher)')
+    p.add_argument('--distill-temp', type=float, metavar='FLOAT',
+                   help='(build extension) temperature of the soft term, > 0 (default 1)')
+    p.add_argument('--label-smoothing', type=float, metavar='FLOAT',
+                   help='(build extension) smooth the hard targets: (1-eps) one-hot + eps/n_quant, eps in [0, 1)')
     p.add_argument('ckpt_path', type=str, metavar='CKPT_PATH_PFX')
     p.add_argument('arch_file', type=str, metavar='ARCH_FILE')
     p.add_argument('par_file', type=str, metavar='PAR_FILE')
@@ -113,12 +135,13 @@ def prepare_arch(arch, num_global_cond):
 OPT_KEYS = ('clip_norm', 'skip_nonfinite', 'ema_decay', 'lr_warmup_steps', 'lr_decay_steps', 'lr_decay_rate',
             'log_grad_norm')
 VALID_KEYS = ('valid_file', 'valid_interval', 'valid_batches', 'valid_ema')
+DISTILL_KEYS = ('teacher_arch', 'teacher_ckpt', 'teacher_ema', 'distill_alpha', 'distill_temp', 'label_smoothing')
 
 
 def override_par(args, par):
     """Command-line values replace the PAR_FILE's keys of the same name (a flag not given leaves the key)."""
     for flag, key in (('batch_size', 'batch_sz'), ('slice_size', 'slice_sz'), ('l2_factor', 'l2_factor'),
-                      ('learning_rate', 'learning_rate')) + tuple((k, k) for k in OPT_KEYS + VALID_KEYS):
+                      ('learning_rate', 'learning_rate')) + tuple((k, k) for k in OPT_KEYS + VALID_KEYS + DISTILL_KEYS):
         if getattr(args, flag) is not None:
             par[key] = getattr(args, flag)
     return par
@@ -153,6 +176,67 @@ def valid_options(par, eval_only=False):
         print('Error: --valid-ema needs an EMA of the weights (--ema-decay)', file=sys.stderr)
         sys.exit(1)
     return vf, interval, int(batches) if batches is not None else None, ema
+
+
+def distill_options(par, eval_only=False):
+    """The distillation / label-smoothing options from the par dict:
+    dict(teacher_arch, teacher_ckpt, teacher_ema, alpha, temp, smoothing), teacher_arch None without a
+    teacher.  Errors print to stderr and exit(1) like the others, before a GPU is needed."""
+    import math
+
+    def fail(msg):
+        print('Error: ' + msg, file=sys.stderr)
+        sys.exit(1)
+
+    ta, tc = par.get('teacher_arch'), par.get('teacher_ckpt')
+    alpha, temp, eps = par.get('distill_alpha'), par.get('distill_temp'), par.get('label_smoothing')
+    if tc and not ta:
+        fail('--teacher-ckpt needs --teacher-arch')
+    if ta and not tc:
+        fail('--teacher-arch needs --teacher-ckpt')
+    if not ta:
+        if par.get('teacher_ema'):
+            fail('--teacher-ema needs a teacher (--teacher-arch, --teacher-ckpt)')
+        if alpha is not None and float(alpha) > 0:
+            fail('--distill-alpha needs a teacher (--teacher-arch, --teacher-ckpt)')
+        if temp is not None:
+            fail('--distill-temp needs a teacher (--teacher-arch, --teacher-ckpt)')
+    elif eval_only:
+        fail('a teacher (--teacher-arch) cannot be combined with --eval-only: the evaluation scores the net alone')
+    alpha = float(alpha) if alpha is not None else (0.5 if ta else 0.0)
+    temp = float(temp) if temp is not None else 1.0
+    eps = float(eps) if eps is not None else 0.0
+    if not 0.0 <= alpha <= 1.0:
+        fail('--distill-alpha must be in [0, 1]')
+    if not (math.isfinite(temp) and temp > 0.0):
+        fail('--distill-temp must be finite and > 0')
+    if not 0.0 <= eps < 1.0:
+        fail('--label-smoothing must be in [0, 1)')
+    return dict(teacher_arch=ta or None, teacher_ckpt=tc or None, teacher_ema=bool(par.get('teacher_ema', False)),
+                alpha=alpha, temp=temp, smoothing=eps)
+
+
+def load_teacher(opts, num_global_cond, batch_sz, log):
+    """The teacher net of --teacher-arch with the weights of --teacher-ckpt (its EMA shadows with
+    --teacher-ema).  Its SAVE is not taken from that checkpoint: the distiller keeps its own."""
+    from lbwn.ckpt import load_tensors
+    from lbwn.optim import EMA_SUFFIX
+    from lbwn.tmodel import WaveNetTrain
+    import torch
+    with open(opts['teacher_arch']) as fp:
+        tarch = prepare_arch(json.load(fp), num_global_cond)
+    teacher = WaveNetTrain(**tarch, batch_sz=batch_sz, l2_factor=0.0, print_interval=0)
+    loaded = load_tensors(opts['teacher_ckpt'])
+    suffix = EMA_SUFFIX if opts['teacher_ema'] else ''
+    with torch.no_grad():
+        for name, dst in teacher.vars.items():
+            src = loaded.get(name + suffix)
+            if src is None or tuple(src.shape) != tuple(dst.shape):
+                print('Error: --teacher-ckpt {} {} {}{}'.format(
+                    opts['teacher_ckpt'], 'lacks' if src is None else 'has another shape for', name, suffix), file=log)
+                sys.exit(1)
+            dst.copy_(src.to(dst.dtype))
+    return teacher
 
 
 def valid_files(sam_file, want_mel):
@@ -200,6 +284,7 @@ def main(argv=None):
     if args.eval_only and not args.resume_step:
         print('Error: --eval-only needs --resume-step', file=stderr)
         sys.exit(1)
+    distill = distill_options(par, args.eval_only)
 
     import torch
     from lbwn import dist as lbdist
@@ -231,7 +316,17 @@ def main(argv=None):
                        print_interval=args.progress_interval if dp.rank == 0 else 0,
                        seed=args.seed if args.seed is not None else 0)
     net.dp = dp
-    dset.set_receptive_field_size(net.get_recep_field_sz())
+    distiller = None
+    if distill['teacher_arch']:
+        from lbwn.distill import Distiller
+        try:
+            distiller = Distiller(net, load_teacher(distill, args.num_global_cond, B, stderr), distill['alpha'],
+                                  distill['temp'], distill['smoothing'])
+        except ValueError as e:
+            print('Error: {}'.format(e), file=stderr)
+            sys.exit(1)
+    # with a teacher the invalid-window mask covers the deeper of the two nets
+    dset.set_receptive_field_size(distiller.recep_field_sz() if distiller else net.get_recep_field_sz())
     dset.build()
     dset.init_vars()
     try:
@@ -244,7 +339,9 @@ def main(argv=None):
     print('Built graph.', file=stderr)
 
     if args.resume_step:
-        net.restore(optimizer)
+        loaded = net.restore(optimizer)
+        if distiller:
+            distiller.load_state_tensors(loaded, log=stderr if dp.rank == 0 else open(os.devnull, 'w'))
         dset.restore()
         print('Restored net and dset from checkpoint', file=stderr)
         if log_norm:
@@ -293,7 +390,10 @@ def main(argv=None):
             file_read_count, wav_input, mel_input, id_mask = next(itr)
         except StopIteration:
             break
-        net.forward(wav_input, mel_input, id_mask, backward=True)
+        if distiller:
+            distiller.step(wav_input, mel_input, id_mask, backward=True)
+        else:
+            net.forward(wav_input, mel_input, id_mask, backward=True, label_smoothing=distill['smoothing'])
         dp.reduce_grads(net)
         if args.progress_interval and net.global_step_host % args.progress_interval == 0:
             net.check_status()                # cumulative: any timed-out step since the start (never applied)
@@ -314,7 +414,8 @@ def main(argv=None):
             validate(step)
         if step % args.save_interval == 0 and step != args.resume_step:
             net.check_status()
-            net_save_path = net.save(step, optimizer)        # collective under DP
+            # collective under DP; with a teacher its SAVE rides along under TEACHER/
+            net_save_path = net.save(step, optimizer, more=distiller.state_tensors() if distiller else None)
             if dp.rank == 0:
                 dset_save_path = dset.save(step, file_read_count)
                 print('Saved checkpoints to {} and {}'.format(net_save_path, dset_save_path), file=stderr)
