@@ -140,33 +140,8 @@ __global__ __launch_bounds__(256) void pre_grad_reduce_kernel(
 // ---- softmax cross-entropy head ------------------------------------------------------------
 // One wave per position row; dlogits (unnormalised) written in place.
 
-// wave-wide max / min / sum on DPP (quad xor 1, 2, row_half_mirror, row_mirror: every row of 16
-// uniform) and the four row values by readlane: one VALU latency per step instead of a ds_bpermute
-// round trip per __shfl step (head_reg_kernel: 23.6 -> 21.3 us at C2, same box).  The sum order is
-// fixed: quads, pairs of quads, half rows, then rows 0 + 1 + 2 + 3.
-template <int CTRL>
-LBWN_DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-LBWN_DEV float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-LBWN_DEV float wave_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-LBWN_DEV int wave_min(int v) {
-  v = min(v, dpp_i<0xB1>(v));
-  v = min(v, dpp_i<0x4E>(v));
-  v = min(v, dpp_i<0x141>(v));
-  v = min(v, dpp_i<0x140>(v));
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
+// wave-wide sum beside common.h's wave_max / wave_min.  The order is fixed: quads, pairs of quads,
+// half rows, then rows 0 + 1 + 2 + 3.
 LBWN_DEV float wave_sum(float v) {
   v += dpp_f<0xB1>(v);
   v += dpp_f<0x4E>(v);
