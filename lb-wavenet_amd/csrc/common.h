@@ -84,7 +84,7 @@ LBWN_DEV float gate_z(float a, float b) {
 // wave-wide max / min on DPP (quad xor 1, 2, row_half_mirror, row_mirror: every row of 16 uniform)
 // and the four row values by readlane: one VALU latency per step instead of a ds_bpermute round
 // trip per __shfl step (head_reg_kernel: 23.6 -> 21.3 us at C2, same box).  No wave_sum here: the
-// head's (misc.hip) adds the rows as ((r0+r1)+r2)+r3, the draw's (gen_draw.h) as (r0+r1)+(r2+r3),
+// head's (head.hip) adds the rows as ((r0+r1)+r2)+r3, the draw's (gen_draw.h) as (r0+r1)+(r2+r3),
 // and bitwise tests pin both orders.
 template <int CTRL, int ROWS = 0xF>
 LBWN_DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROWS, 0xF, true); }
@@ -108,6 +108,25 @@ LBWN_DEV int wave_min(int v) {
   v = min(v, dpp_i<0x140>(v));
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// a 256-thread block's doubles summed in LDS by halving strides (a fixed order); every thread returns the total
+LBWN_DEV double block_sum256(double s, double* sh) {
+  sh[threadIdx.x] = s;
+  __syncthreads();
+#pragma unroll
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// 1-D grid of `per`-item blocks over n items, at least 1 and at most `cap` blocks (grid-stride kernels)
+static inline int lbwn_grid_for(long n, int per = 256, int cap = 8192) {
+  long g = (n + per - 1) / per;
+  if (g < 1) g = 1;
+  return (int)(g > cap ? cap : g);
 }
 
 // Host-side error plumbing (defined in capi.cpp).

@@ -1035,6 +1035,18 @@ static int forward_to_logits(lbwn_plan* p, const lbwn_params* P, void* ws, const
   return 0;
 }
 
+// The fields lbwn_head_args and lbwn_head_ex_args share (two structs, not one inside the other: each
+// kernel keeps its argument layout), and the plan's note of the column partials the head will write.
+template <class H>
+static void head_common(lbwn_plan* p, void* ws, const int* wav_q, const int* ids, H& h) {
+  h.logits = at<float>(ws, p->oLOG); h.q = wav_q; h.ids = ids; h.B = p->B; h.T = p->T; h.Q = p->Q;
+  h.partial = at<float>(ws, p->oHEADP);
+  // the post2 bias gradient's column partials from the head itself (bf16-split form, Q <= 512),
+  // summed in the backward by colsum_final: no colsum pass over dlogits
+  h.colpart = (lbwn_gemm_mode() == 1 && p->Q <= 512) ? at<float>(ws, p->oCOLS) : nullptr;
+  p->head_colparts = h.colpart ? lbwn_head_nblocks(p->M, true) : 0;
+}
+
 int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* wav_q, const int* ids,
                        const float* mel, float* save, float* stats, void* stream) {
   LBWN_REQUIRE(p && P && ws && wav_q && ids && save && stats, "train_forward: null argument");
@@ -1042,17 +1054,10 @@ int lbwn_train_forward(lbwn_plan* p, const lbwn_params* P, void* ws, const int* 
   hipStream_t st = (hipStream_t)stream;
   int e;
   if ((e = forward_to_logits(p, P, ws, wav_q, ids, mel, save, st))) return e;
-  const int B = p->B, T = p->T;
-  const long M = p->M;
-  float* LOG = at<float>(ws, p->oLOG);
   // masked softmax-xent (+ unnormalised dlogits in place)  (tmodel.py:228-249)
   lbwn_head_args h;
-  h.logits = LOG; h.q = wav_q; h.ids = ids; h.B = B; h.T = T; h.Q = p->Q;
-  h.partial = at<float>(ws, p->oHEADP); h.write_grad = 1;
-  // the post2 bias gradient's column partials from the head itself (bf16-split form, Q <= 512),
-  // summed in the backward by colsum_final: no colsum pass over dlogits
-  h.colpart = (lbwn_gemm_mode() == 1 && p->Q <= 512) ? at<float>(ws, p->oCOLS) : nullptr;
-  p->head_colparts = h.colpart ? lbwn_head_nblocks(M, true) : 0;
+  head_common(p, ws, wav_q, ids, h);
+  h.write_grad = 1;
   int nb = 0;
   Probe(p, st, "head");
   if ((e = lbwn_head_launch(h, &nb, st))) return e;
@@ -1095,15 +1100,11 @@ int lbwn_train_forward_ex(lbwn_plan* p, const lbwn_params* P, void* ws, const lb
   hipStream_t st = (hipStream_t)stream;
   int e;
   if ((e = forward_to_logits(p, P, ws, a->wav_q, a->ids, a->mel, a->save, st))) return e;
-  const long M = p->M;
-  float* colpart = (lbwn_gemm_mode() == 1 && p->Q <= 512) ? at<float>(ws, p->oCOLS) : nullptr;
-  p->head_colparts = colpart ? lbwn_head_nblocks(M, true) : 0;
   int nb = 0;
   if (alpha == 0.f && eps == 0.f) {   // no option active: lbwn_train_forward's head
     lbwn_head_args h;
-    h.logits = at<float>(ws, p->oLOG); h.q = a->wav_q; h.ids = a->ids; h.B = p->B; h.T = p->T; h.Q = p->Q;
-    h.partial = at<float>(ws, p->oHEADP); h.write_grad = 1;
-    h.colpart = colpart;
+    head_common(p, ws, a->wav_q, a->ids, h);
+    h.write_grad = 1;
     Probe(p, st, "head");
     if ((e = lbwn_head_launch(h, &nb, st))) return e;
     Probe::end(p, st, "head");
@@ -1111,15 +1112,13 @@ int lbwn_train_forward_ex(lbwn_plan* p, const lbwn_params* P, void* ws, const lb
     return lbwn_stats_reduce_ex_launch(h.partial, nullptr, nb, a->stats, a->stats_ex, st);
   }
   lbwn_head_ex_args h;
-  h.logits = at<float>(ws, p->oLOG); h.q = a->wav_q; h.ids = a->ids; h.B = p->B; h.T = p->T; h.Q = p->Q;
+  head_common(p, ws, a->wav_q, a->ids, h);
   h.teacher = alpha > 0.f ? a->teacher_logits : nullptr;   // alpha = 0: nothing of the teacher is read
   h.ld_teacher = (long)a->ld_teacher;
   h.alpha = alpha; h.temp = temp; h.inv_temp = 1.f / temp; h.eps = eps;
-  h.partial = at<float>(ws, p->oHEADP);
   // the two further partials per block live in "dh", which the backward writes before it reads:
   // at most 2·ceil(M/4) floats of its M·n_post (M >= 4), so no plan's workspace grows
   h.partial_ex = at<float>(ws, p->oDH);
-  h.colpart = colpart;
   Probe(p, st, "head");
   if ((e = lbwn_head_ex_launch(h, &nb, st))) return e;
   Probe::end(p, st, "head");

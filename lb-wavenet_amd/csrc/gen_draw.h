@@ -35,7 +35,7 @@ LBWN_DEV float wave_scan(float x) {
   return x;
 }
 // wave-wide sum, the same value on every lane (each step adds a lane's partner, so both sides of a
-// pair form the same sum): the filtered draw's masses.  Rows added as (r0+r1)+(r2+r3): not misc.hip's
+// pair form the same sum): the filtered draw's masses.  Rows added as (r0+r1)+(r2+r3): not head.hip's
 LBWN_DEV float wave_sum(float v) {
   v += dpp_f<0xB1>(v);
   v += dpp_f<0x4E>(v);

@@ -261,7 +261,7 @@ int lbwn_head_ex_launch(const lbwn_head_ex_args& a, int* nblocks_out, hipStream_
 int lbwn_stats_reduce_ex_launch(const float* partial, const float* partial_ex, int nparts, float* stats,
                                 float* stats_ex, hipStream_t st);
 
-// lbwn_train_eval's head (misc.hip): the xent of the training head with no gradient written, per-block
+// lbwn_train_eval's head (head.hip): the xent of the training head with no gradient written, per-block
 // partials in double, then a fixed-order fold into acc / by_voice
 struct lbwn_eval_head_args {
   const float* logits;      // [M][Q], read only

@@ -82,7 +82,7 @@ LBWN_DEV void zero_body(long blk, long nblk, unsigned* p, long n) {
 }
 
 // ---- live lists of the masked-position skip --------------------------------------------------
-// Row m = (b, t) of the step is valid iff t < T-1 and ids[min(m+1, M-1)] != 0 (misc.hip
+// Row m = (b, t) of the step is valid iff t < T-1 and ids[min(m+1, M-1)] != 0 (head.hip
 // head_reg_kernel; tmodel.py:231-232); the head writes dlogits = 0 at every other row, so the
 // backward's dH1 / dS / dZ rows there are exactly zero.  tlive[ceil(M/256)]: 1 = the 256-row tile
 // holds a valid row; klive: the ascending list of the 32-row k-steps that hold one, nklive its

@@ -256,7 +256,7 @@ def launch(lib, P, akc=1, bkc=0, pre=0, split=1, bias=0, mask=0, relu_a=0, relu_
 def check_colpart(lib, r, M, N):
     """Only the summation is measured: the float64 column sums of the GPU's own C per 256-row
     block, sequential-sum bound 255·2^-24·Σ|C| per column; then lbwn_colsum_final's order on the
-    host (csrc/misc.hip colsum_final_kernel: 16 lanes take every 16th part in order, then the lane
+    host (csrc/reduce.hip colsum_final_kernel: 16 lanes take every 16th part in order, then the lane
     sums in order) against C's whole column sum."""
     parts = r.colpart.reshape(-1, N)
     assert parts.shape[0] == (M + 255) // 256 == lib.lbwn_colpart_parts_abi(M)

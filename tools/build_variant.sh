@@ -13,8 +13,8 @@ for h in "$@"; do
   [ "${h##*.}" = h ] && git show $REV:lb-wavenet_amd/csrc/$h > build/var_$NAME/$h
 done
 OBJS=""
-for f in gemm layer pack chain_fwd chain_bwd misc gen gen_step gen_persist gen_prefill gen_state cond mel engine capi \
-         mel_plan; do   # the Makefile's objects
+for f in gemm layer pack chain_fwd chain_bwd misc head optim reduce gen gen_step gen_persist gen_prefill gen_state cond \
+         mel engine capi mel_plan; do   # the Makefile's objects
   src=$f.hip; [ -f $src ] || src=$f.cpp
   if [[ " $* " == *" $src "* ]]; then
     git show $REV:lb-wavenet_amd/csrc/$src > build/var_$NAME/$src

@@ -40,7 +40,7 @@ def code_objects(path=LIB, arch='gfx950'):
 
 
 def kernel_resources(path=LIB, arch='gfx950'):
-    """{symbol name: {'vgpr': n, 'agpr': n, 'sgpr': n, 'lds': bytes}} over all bundles."""
+    """{symbol name: {'vgpr': n, 'agpr': n, 'sgpr': n, 'lds': bytes, 'scratch': bytes}} over all bundles."""
     res = {}
     for img in code_objects(path, arch):
         with tempfile.NamedTemporaryFile(suffix='.co') as f:
@@ -57,7 +57,8 @@ def kernel_resources(path=LIB, arch='gfx950'):
                 m = re.search(r'\.%s:\s+(\d+)' % key, blk)
                 return int(m.group(1)) if m else 0
             res[name.group(1)] = {'vgpr': num('vgpr_count'), 'agpr': num('agpr_count'),
-                                  'sgpr': num('sgpr_count'), 'lds': num('group_segment_fixed_size')}
+                                  'sgpr': num('sgpr_count'), 'lds': num('group_segment_fixed_size'),
+                                  'scratch': num('private_segment_fixed_size')}
     return res
 
 
