@@ -358,7 +358,9 @@ size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* plan);
 /* "samples" int32 [B][max_steps] (drawn µ-law codes), "wav" fp32 [B][max_steps]
  * (mu_decode of the draws, imodel.py:181-182), "logits" [B][Q] (last step), "step" int64,
  * "rings" (lookback state, SAVE layout), "teacher" int32, "status" int32 (0; 5 when a persistent
- * hand-off timed out; 6 when lbwn_gen_state_load refused its snapshot or map); LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
+ * hand-off timed out; 6 when lbwn_gen_state_load refused its snapshot or map; 7 when lbwn_gen_extend or
+ * lbwn_gen_collect refused its range on the device); ring plans (lbwn_gen_plan_create_ex) size "samples", "wav"
+ * and "lc" by their ring instead; LC plans also "lc" fp32, ceil(max_steps/hop)·hop rows per stream reserved
  * ([B][rows][n_lc_out] bytes), of which lbwn_gen_set_mel fills the first B·n_frames·hop rows
  * densely as [B][n_frames·hop][n_lc_out], and "lccond" fp32 [NC][L][B][64] (slot = step mod NC;
  * columns: signal 0..31 | gate 32..63, zero past n_dil) and "pfcond" fp32 [B·T_s][G·2·n_dil], the
@@ -513,7 +515,9 @@ int lbwn_gen_get_sampling(const lbwn_gen_plan* plan, float* temperature, int* to
  * memory, so the load's launch checks it before it writes: magic, version, n_blocks, n_block_layers,
  * n_res, n_quant and record_bytes against the plan, n_streams against state_streams, 0 <= step <=
  * max_steps, every map entry in range.  On a mismatch "status" becomes 6 and nothing else in the
- * workspace changes; the step launches stop on a nonzero status and lbwn_gen_start clears it. */
+ * workspace changes; lbwn_gen_start clears it.  A nonzero status does not stop a lbwn_gen_run on a plan without
+ * a ring (it only makes the persistent form's spinning hand-offs give up): check "status" before trusting what
+ * follows.  On a ring plan (below) a lbwn_gen_run takes no step while the status is nonzero. */
 size_t lbwn_gen_state_bytes(const lbwn_gen_plan* plan, int n_streams);
 int lbwn_gen_state_save(const lbwn_gen_plan* plan, const void* workspace, void* state, void* stream);
 int lbwn_gen_state_load(lbwn_gen_plan* plan, void* workspace, const void* state, int state_streams,
@@ -534,7 +538,8 @@ int lbwn_gen_state_load(lbwn_gen_plan* plan, void* workspace, const void* state,
  *     n_frames·hop - 1), lbwn_gen_set_mel's rule per session.
  * "samples" and "wav" stay [B][max_steps] indexed by the absolute step: a session's j-th sample is column
  * base_b + j.  The other streams, their "logits", the step counter, "status", the hand-off granules and the
- * sampling settings are untouched.  A run does not outlive max_steps: size it for the whole schedule.
+ * sampling settings are untouched.  On a plan without a ring a run does not outlive max_steps: size it for
+ * the whole schedule, or make a ring plan (lbwn_gen_plan_create_ex below), whose columns are i mod R.
  * The words live in "sessions", int64 [B][4] = {base, key, rows = n_frames·hop, 0}: the last 32·B bytes
  * (rounded up to 256) of the workspace, over the tail of the prefill scratch, so the workspace size of a
  * plan is what it was (a plan whose prefill scratch is smaller than the words grows by the difference).
@@ -571,6 +576,82 @@ typedef struct lbwn_gen_session {
 } lbwn_gen_session;
 int lbwn_gen_begin(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const lbwn_gen_session* s,
                    int n, size_t struct_size, void* stream);
+/* Ring plans: outputs and conditioning addressed by the session's local step modulo a capacity chosen at
+ * plan creation, so the workspace does not depend on how long the process runs (added after ABI 5 was
+ * declared, same ABI: three symbols added, none altered).
+ * lbwn_gen_plan_create_ex with ring_steps == 0 is lbwn_gen_plan_create(arch, batch_sz, max_steps,
+ * max_teacher, out): the same workspace, kernels and bits.  ring_steps = R >= 1 makes a ring plan:
+ *   "samples" and "wav" are [B][R]; the sample of a stream's local step i = t - base_b lies in column
+ *     i mod R (base_b = 0 until a lbwn_gen_begin, as lbwn_gen_start stands for).  Every step stores; no
+ *     step is dropped for lying past max_steps, which a ring plan ignores (for the snapshot check
+ *     0 <= step <= max_steps of lbwn_gen_state_load it is unbounded).  The step counter is bounded by
+ *     int64 only: a run has no end, and nothing needs sizing for the schedule.
+ *   LC plans: "lc" is [B][Rlc][n_lc_out], Rlc = ceil(R/hop)·hop (< 2^31), and the upsample stages' scratch
+ *     holds Rlc/hop frames per stream.  In session mode local row r of a stream lies at row r mod Rlc of
+ *     its own region; a lbwn_gen_begin may bring at most Rlc/hop frames (more come by lbwn_gen_extend).
+ *     lbwn_gen_set_mel keeps its dense layout [B][n_frames·hop][n_lc_out] and its bound n_frames·hop <=
+ *     Rlc, under which r mod Rlc = r.
+ *   lbwn_gen_workspace_bytes does not depend on max_steps; lbwn_gen_tensor reports the sizes above.
+ *   EINVAL on a ring plan, before any launch: lbwn_gen_prefill and lbwn_gen_score (both stay whole-batch
+ *     operations over absolute steps), a teacher (lbwn_gen_start with n_teacher > 0: the override is keyed
+ *     by the absolute step), and lbwn_gen_state_load in session mode on an LC plan (below).
+ * EINVAL from lbwn_gen_plan_create_ex: arch, args or out NULL, struct_size != sizeof(lbwn_gen_plan_args),
+ * ring_steps < 0, Rlc >= 2^31, and every refusal of lbwn_gen_plan_create.
+ *
+ * lbwn_gen_extend appends n_frames more mel frames to the live session of each listed stream: the plan's
+ * upsample stack (as in lbwn_gen_begin) into local rows [rows_b, rows_b + n_frames·hop) of the stream's
+ * region -- on a ring plan in at most two pieces where the range wraps; hop divides Rlc, so no frame
+ * straddles the wrap -- and rows_b += n_frames·hop in the session words, on the device.  The plan keeps a
+ * host mirror of every slot's row count for the destination (lbwn_gen_begin and lbwn_gen_extend are its
+ * only writers; lbwn_gen_start clears it; it is advanced with each check launch, so it equals the row words
+ * of every run that the device has not refused).  On a plan without a ring the bound is the reserved rows (EINVAL
+ * from the mirror).  On a ring plan the rows a stream has already read are known on the device only (a
+ * captured lbwn_gen_run replays without the host), so the call's first launch checks there: with i the
+ * stream's local step and r = min(max(i - 1, 0), rows_b) the row that step reads (rows_b: every row given
+ * so far is behind it), rows_b + n_frames·hop - r > Rlc sets "status" to 7 and advances no row word of that
+ * launch (neither does a launch that finds the status nonzero already).  The upsample launches of a refused
+ * call still run (the host cannot see the refusal) and may overwrite unread rows; the run is dead anyway:
+ * on a ring plan a lbwn_gen_run takes no step (the counter stays, nothing is drawn) while the status is
+ * nonzero, in both execution forms, until lbwn_gen_start clears it (a plan without a ring runs on, as after
+ * status 6: check "status").
+ * One check-and-advance launch per call (one per 128 streams) plus each piece's upsample launches;
+ * stream-ordered, no allocation, no host synchronisation; valid between replays of a captured lbwn_gen_run.
+ * EINVAL before any launch, naming the argument: plan, params, workspace or e NULL; struct_size !=
+ * sizeof(lbwn_gen_extend_entry); n < 1 or n > batch_sz; an arch without LC; a slot outside [0, batch_sz),
+ * listed twice or whose stream has begun no session since lbwn_gen_start; mel NULL or not 16-byte aligned;
+ * n_frames < 1; n_frames·hop beyond Rlc (ring) or rows_b + n_frames·hop beyond the reserved rows (no ring).
+ *
+ * lbwn_gen_collect copies local steps [i0, i0 + n) of stream `slot` out of "wav" and "samples" into dense
+ * caller buffers (device memory; either may be NULL), one launch.  The stream's base and the step counter
+ * are read on the device: with e = step - base_b the local steps already run, the range must satisfy
+ * i0 + n <= e and, on a ring plan, i0 >= e - R (not yet overwritten); on a plan without a ring, base_b + i0
+ * + n <= max_steps.  Otherwise "status" becomes 7 and nothing is written.  Without a ring it is the same
+ * copy without the wrap.  EINVAL before any launch: plan or workspace NULL, slot outside [0, batch_sz),
+ * i0 < 0, n < 0, both outputs NULL (n == 0 launches nothing).
+ *
+ * lbwn_gen_state_save / _load on a ring plan: as documented, the session words are not carried, and neither
+ * is the host row mirror.  An identity rewind (save, run, load, run, no begin or extend in between) repeats
+ * the run bit for bit, "samples" and "wav" columns included, when the plan has no LC, is on the
+ * lbwn_gen_set_mel path, or is not a ring plan.  On a ring LC plan in session mode the rows the rewound
+ * steps read may have been overwritten by later extends and the mirror would be ahead of the words, so
+ * lbwn_gen_state_load is EINVAL there. */
+typedef struct lbwn_gen_plan_args {
+  size_t struct_size;   /* sizeof(lbwn_gen_plan_args) */
+  int batch_sz;
+  int64_t max_steps;    /* as lbwn_gen_plan_create; ignored by a ring plan (>= 1 all the same) */
+  int64_t max_teacher;
+  int64_t ring_steps;   /* 0: no ring (lbwn_gen_plan_create); R >= 1: a ring plan */
+} lbwn_gen_plan_args;
+int lbwn_gen_plan_create_ex(const lbwn_arch* arch, const lbwn_gen_plan_args* args, lbwn_gen_plan** out);
+typedef struct lbwn_gen_extend_entry {
+  int slot;          /* stream index in [0, batch_sz), with a live session */
+  const float* mel;  /* device fp32 [n_frames][n_lc_in], 16-B aligned: the frames after those already given */
+  int64_t n_frames;  /* >= 1 */
+} lbwn_gen_extend_entry;
+int lbwn_gen_extend(lbwn_gen_plan* plan, const lbwn_params* params, void* workspace, const lbwn_gen_extend_entry* e,
+                    int n, size_t struct_size, void* stream);
+int lbwn_gen_collect(lbwn_gen_plan* plan, void* workspace, int slot, int64_t i0, int64_t n, float* wav_out,
+                     int* samples_out, void* stream);
 
 /* ---- log-mel front end: wav to the LC conditioning, one launch (added after ABI 5 was declared, same
  * ABI: symbols added, none altered) ----

@@ -27,9 +27,12 @@ static int gen_env_int(const char* name, int hi, const char* what, int* v) {
   return 0;
 }
 
-extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps, int64_t max_teacher,
-                                    lbwn_gen_plan** out) {
+// ring = 0: the plan of lbwn_gen_plan_create; ring = R >= 1: a ring plan, whose outputs hold R
+// columns and whose "lc" holds Rlc = ceil(R/hop)·hop rows per stream, whatever max_steps says
+static int gen_plan_make(const lbwn_arch* a, int B, int64_t max_steps, int64_t max_teacher, int64_t ring,
+                         lbwn_gen_plan** out) {
   LBWN_REQUIRE(a && out && B >= 1 && max_steps >= 1 && max_teacher >= 0, "gen_plan_create: bad arguments");
+  const long long cols = ring ? ring : max_steps;   // columns of "samples" / "wav", steps the lc rows cover
   LBWN_REQUIRE(a->n_res <= 32 && a->n_dil <= 32, "gen: n_res/n_dil must be <= 32");
   LBWN_REQUIRE(a->n_blocks * a->n_block_layers <= G_MAXL, "gen: more than %d layers (tap cache)", G_MAXL);
   LBWN_REQUIRE(a->n_quant <= 512, "gen: n_quant must be <= 512");
@@ -47,7 +50,8 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     }
     LBWN_REQUIRE(a->n_lc_in >= 4 && a->n_lc_in % 4 == 0 && a->n_lc_out % 4 == 0,
                  "gen: n_lc_in/n_lc_out must be multiples of 4");
-    LBWN_REQUIRE((max_steps + hop - 1) / hop * hop < (1LL << 31), "gen: max_steps too large for an LC plan");
+    LBWN_REQUIRE(cols < (1LL << 31) && (cols + hop - 1) / hop * hop < (1LL << 31), "gen: %s too large for an LC plan",
+                 ring ? "ring_steps" : "max_steps");
     if (int e = gen_env_int("LBWN_GEN_LC_CHUNK", G_LC_CHUNK_MAX, "", &lc_chunk)) return e;
     LBWN_REQUIRE((long long)lc_chunk * B / LCP_ROWS < 65535, "gen: LBWN_GEN_LC_CHUNK %d x batch_sz %d is too large",
                  lc_chunk, B);   // the projection's grid: one block row per LCP_ROWS (step, stream) pairs
@@ -62,7 +66,8 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   p->nbl = a->n_block_layers;
   p->L = a->n_blocks * a->n_block_layers;
   p->Cr = a->n_res; p->Cd = a->n_dil; p->Cs = a->n_skip; p->Cp = a->n_post; p->Q = a->n_quant;
-  p->max_steps = max_steps;
+  p->max_steps = ring ? INT64_MAX : max_steps;
+  p->ring = ring;
   p->max_teacher = max_teacher;
   long dsum = (long)a->n_blocks * ((1L << a->n_block_layers) - 1);
   p->n_ring = dsum * B * p->Cr;
@@ -81,8 +86,8 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   p->oSTEP = gcarve(cur, 16);   // step counter + status word
   p->oCODE = gcarve(cur, 4 * (size_t)B);
   p->oTEACH = gcarve(cur, 4 * (size_t)std::max<int64_t>(1, max_teacher));
-  p->oSAMP = gcarve(cur, 4 * (size_t)B * max_steps);
-  p->oWAV = gcarve(cur, 4 * (size_t)B * max_steps);
+  p->oSAMP = gcarve(cur, 4 * (size_t)B * cols);
+  p->oWAV = gcarve(cur, 4 * (size_t)B * cols);
   p->oGCP = gcarve(cur, 4 * (size_t)p->L * B * 64);
   p->oBSUM = gcarve(cur, 4 * (size_t)p->Cs);
   p->oGIMG = gcarve(cur, 4 * (size_t)p->L * GIMG);
@@ -118,7 +123,7 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
   if (a->n_lc_out > 0) {
     p->Li = a->n_lc_in; p->Lo = a->n_lc_out; p->nup = a->n_lc_upsample; p->hop = hop; p->NC = lc_chunk;
     for (int i = 0; i < p->nup; ++i) p->up[i] = a->lc_upsample[i];
-    const long long frames = (max_steps + hop - 1) / hop;
+    const long long frames = (cols + hop - 1) / hop;
     p->lc_rows = frames * hop;
     p->oLC = gcarve(cur, 4 * (size_t)B * p->lc_rows * p->Lo);
     long long r = frames;
@@ -154,10 +159,28 @@ extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps
     p->oSESS = cur - sb;
     p->sess_begun.assign(B, 0);
     p->sess_seen.assign(B, 0);
+    p->sess_rows.assign(B, 0);
   }
   p->total = cur;
   *out = p;
   return 0;
+}
+
+extern "C" int lbwn_gen_plan_create(const lbwn_arch* a, int B, int64_t max_steps, int64_t max_teacher,
+                                    lbwn_gen_plan** out) {
+  return gen_plan_make(a, B, max_steps, max_teacher, 0, out);
+}
+
+extern "C" int lbwn_gen_plan_create_ex(const lbwn_arch* a, const lbwn_gen_plan_args* args, lbwn_gen_plan** out) {
+  LBWN_REQUIRE(a, "gen_plan_create_ex: arch is null");
+  LBWN_REQUIRE(args, "gen_plan_create_ex: args is null");
+  LBWN_REQUIRE(out, "gen_plan_create_ex: out is null");
+  LBWN_REQUIRE(args->struct_size == sizeof(lbwn_gen_plan_args), "gen_plan_create_ex: struct_size %zu != %zu",
+               args->struct_size, sizeof(lbwn_gen_plan_args));
+  LBWN_REQUIRE(args->ring_steps >= 0, "gen_plan_create_ex: ring_steps = %lld must be >= 0", (long long)args->ring_steps);
+  LBWN_REQUIRE(args->ring_steps < (1LL << 31), "gen_plan_create_ex: ring_steps = %lld must be < 2^31",
+               (long long)args->ring_steps);
+  return gen_plan_make(a, args->batch_sz, args->max_steps, args->max_teacher, args->ring_steps, out);
 }
 
 extern "C" void lbwn_gen_plan_destroy(lbwn_gen_plan* p) { delete p; }
@@ -165,12 +188,13 @@ extern "C" size_t lbwn_gen_workspace_bytes(const lbwn_gen_plan* p) { return p ? 
 
 extern "C" int lbwn_gen_tensor(const lbwn_gen_plan* p, const char* name, size_t* off, size_t* bytes) {
   LBWN_REQUIRE(p && name && off && bytes, "gen_tensor: null argument");
-  const size_t B = p->B;
-  if (!strcmp(name, "samples")) { *off = p->oSAMP; *bytes = 4 * B * p->max_steps; }
-  else if (!strcmp(name, "wav")) { *off = p->oWAV; *bytes = 4 * B * p->max_steps; }
+  const size_t B = p->B, cols = gen_out_cols(p);
+  if (!strcmp(name, "samples")) { *off = p->oSAMP; *bytes = 4 * B * cols; }
+  else if (!strcmp(name, "wav")) { *off = p->oWAV; *bytes = 4 * B * cols; }
   else if (!strcmp(name, "logits")) { *off = p->oLOG; *bytes = 4 * B * p->Q; }
   else if (!strcmp(name, "step")) { *off = p->oSTEP; *bytes = 8; }
-  // 0, or 5: a persistent hand-off timed out, or 6: lbwn_gen_state_load refused its snapshot or map
+  // 0, or 5: a persistent hand-off timed out, or 6: lbwn_gen_state_load refused its snapshot or map, or 7:
+  // lbwn_gen_extend / lbwn_gen_collect refused their range
   else if (!strcmp(name, "status")) { *off = p->oSTEP + 8; *bytes = 4; }
   else if (!strcmp(name, "trace")) { *off = p->oTRACE; *bytes = 8 * (size_t)(2 * p->L + 8 + 128 + 2 * P_NH); }
   else if (!strcmp(name, "rings")) { *off = p->oRING; *bytes = 4 * (size_t)p->n_ring; }

@@ -62,6 +62,12 @@ struct lbwn_gen_plan {
   bool sess_mode = false;
   std::vector<unsigned char> sess_begun, sess_seen;
   int n_begun = 0;
+  // ring plans (lbwn_gen_plan_create_ex): ring = R > 0 makes "samples" / "wav" [B][R], column =
+  // local step mod R, and lc_rows = Rlc = ceil(R/hop)·hop a ring of local rows per stream; max_steps is then
+  // unbounded.  sess_rows: the host mirror of each slot's row count (lbwn_gen_begin and lbwn_gen_extend write
+  // it, lbwn_gen_start clears it): where an extend's rows go
+  long long ring = 0;
+  std::vector<long long> sess_rows;
 };
 
 // What lbwn_gen_run (gen.hip) starts: n_steps steps in the per-step form (gen_step.hip) or in one launch
@@ -70,6 +76,9 @@ int lbwn_gen_step_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_st
 int lbwn_gen_persist_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n_steps, hipStream_t st);
 int lbwn_gen_decode_launch(const lbwn_gen_plan* p, void* ws, int n_steps, hipStream_t st);
 int lbwn_gen_lc_proj_launch(const lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n, hipStream_t st);
+
+// columns of "samples" / "wav": the ring's R, else max_steps
+static long long gen_out_cols(const lbwn_gen_plan* p) { return p->ring ? p->ring : p->max_steps; }
 
 static size_t gcarve(size_t& cur, size_t bytes) {
   size_t o = cur;
@@ -118,6 +127,13 @@ constexpr int P_NH = 32;     // head blocks
 constexpr int P_MAXB = 16;   // streams per group (phase A maps 16 columns x 16 streams onto 512 threads)
 constexpr int P_MAXL = 236;  // layers (the draw's two half-sums use tap-table rows 240..255)
 constexpr int LCP_ROWS = 64;   // (step, stream) rows per block of gen_lc_proj_kernel
+
+// ring plans: i mod R for a local step or row i >= 0 and a ring of R < 2^31 -- the 32-bit division while i
+// fits (the first 2^32 steps of a session, 74 hours at 16 kHz), the 64-bit one after that
+LBWN_DEV unsigned ring_col(long long i, unsigned R) {
+  const unsigned long long u = (unsigned long long)i;
+  return (u >> 32) == 0 ? (unsigned)u % R : (unsigned)(u % R);
+}
 
 // ---- device helpers of both chains (gen_wave_kernel, persist_chain) -------------------------
 // Wave-level LDS sync for single-wave workgroups: orders the wave's own LDS traffic without

@@ -14,9 +14,12 @@ namespace {
 // transform).  Wave-level only — lane = a contiguous run of ceil(Q/64) codes, shuffles, no
 // workgroup barrier — so every wave that calls it with the same logits draws the same code.
 struct DrawK {
-  const float* part; int parts; const float* bias;   // logits = Σ part[p][b][:] + bias (per-step path)
+  const float* part; int parts;   // logits = Σ part[p][b][:] + bias (per-step path)
+  unsigned ring;                  // ring plans: R, column = local step mod R (0: none); in the struct's padding, so
+  const float* bias;              // no other member moves
   int Q, B;
-  float* logits; int* samples; float* wav; long long max_steps;
+  float* logits; int* samples; float* wav;
+  long long max_steps;   // columns of samples / wav, by the absolute step (0 on a ring plan: ring says where)
   const int* teacher; long long n_teacher; unsigned long long seed; int* code;
   float temperature; int top_k; float top_p;   // lbwn_gen_set_sampling; read by the FILT forms only
   // sessions (lbwn_gen_begin): [B][4] int64 {base, key, rows, 0}, or null: key = stream, base = 0
@@ -64,13 +67,19 @@ LBWN_DEV float mu_decode_q(int q, int Q) {
 }
 
 // the end of both draws: the next input code of stream b after step t (the teacher's or the draw);
-// the writing wave's lane 0 stores the sample, its µ-law decode and code[b]
+// the writing wave's lane 0 stores the sample, its µ-law decode and code[b].  RING = false leaves out the ring
+// plans' store (the persistent kernel's instantiations for plans without a ring).
+template <bool RING>
 LBWN_DEV int draw_commit(const DrawK& a, int b, long long t, int found, bool write, bool decode) {
   const int next = (t < a.n_teacher) ? a.teacher[t] : found;   // imodel.py:260-269
   if (write && (threadIdx.x & 63) == 0) {
     if (t < a.max_steps) {
       a.samples[(long)b * a.max_steps + t] = found;
       if (decode) a.wav[(long)b * a.max_steps + t] = mu_decode_q(found, a.Q);
+    } else if (RING && a.ring) {   // ring plan: every step stored
+      const long c = (long)b * a.ring + ring_col(t - (a.sess ? a.sess[4 * b] : 0LL), a.ring);
+      a.samples[c] = found;
+      if (decode) a.wav[c] = mu_decode_q(found, a.Q);
     }
     a.code[b] = next;
   }
@@ -79,7 +88,7 @@ LBWN_DEV int draw_commit(const DrawK& a, int b, long long t, int found, bool wri
 
 // v[j] = logit of code lane·per + j.  Returns draw_commit's next input code; the writing wave also
 // stores the logits.
-template <int MP>
+template <int MP, bool RING = true>
 LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool write, bool decode = true) {
   const int lane = threadIdx.x & 63, Q = a.Q;
   const int per = (Q + 63) >> 6, c0 = lane * per;
@@ -124,7 +133,7 @@ LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool 
   }
   found = wave_min(found);
   if (found >= Q) found = Q - 1;
-  return draw_commit(a, b, t, found, write, decode);
+  return draw_commit<RING>(a, b, t, found, write, decode);
 }
 
 // The filtered draw (lbwn_gen_set_sampling: temperature T, top_k, top_p), same
@@ -141,7 +150,7 @@ LBWN_DEV int draw_core(float (&v)[MP], const DrawK& a, int b, long long t, bool 
 //          (e <= 1 < 2^30 as bits) of a masked wave sum.  Kept: bits(e) >= th, its ties included.
 // The inverse-CDF walk is draw_core's over the surviving e; its rounding fallbacks (no lane or no
 // code crossing the target) take the last SURVIVING code, never a filtered one.
-template <int MP>
+template <int MP, bool RING = true>
 LBWN_DEV int draw_core_filt(float (&v)[MP], const DrawK& a, int b, long long t, bool write, bool decode = true) {
   const int lane = threadIdx.x & 63, Q = a.Q;
   const int per = (Q + 63) >> 6, c0 = lane * per;
@@ -220,7 +229,7 @@ LBWN_DEV int draw_core_filt(float (&v)[MP], const DrawK& a, int b, long long t, 
   }
   found = wave_min(found);
   if (found >= Q) found = -wave_min(-lastc);   // target rounded up to the total: the last survivor
-  return draw_commit(a, b, t, found, write, decode);
+  return draw_commit<RING>(a, b, t, found, write, decode);
 }
 
 // the draw's arguments of a run in either form (part / parts: the per-step form sets them)
@@ -229,7 +238,7 @@ DrawK draw_args(const lbwn_gen_plan* p, const lbwn_params* P, void* ws) {
   memset(&d, 0, sizeof(d));
   d.Q = p->Q; d.B = p->B; d.bias = P->post2_b;
   d.logits = gat<float>(ws, p->oLOG); d.samples = gat<int>(ws, p->oSAMP); d.wav = gat<float>(ws, p->oWAV);
-  d.max_steps = p->max_steps; d.teacher = gat<int>(ws, p->oTEACH); d.n_teacher = p->n_teacher; d.seed = p->seed;
+  d.max_steps = p->ring ? 0 : p->max_steps; d.ring = (unsigned)p->ring; d.teacher = gat<int>(ws, p->oTEACH); d.n_teacher = p->n_teacher; d.seed = p->seed;
   d.code = gat<int>(ws, p->oCODE);
   d.temperature = p->temperature; d.top_k = p->top_k; d.top_p = p->top_p;
   d.sess = p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr;

@@ -96,7 +96,7 @@ LBWN_DEV void dma4_sc1(const float* src, float* lds_dst) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 16);
 }
 
-template <bool LC, bool FILT>
+template <bool LC, bool FILT, bool RP>
 LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* stepc, long long* trace) {
   float* RING = sm;                  // [G_NS][G_SLOT]
   float* XP = sm + G_NS * G_SLOT;    // [L][32] dilated taps of this step
@@ -236,8 +236,8 @@ LBWN_DEV void persist_chain(const PersistK& a, float* sm, int b, long long* step
         lv[j] = DL[cc] + DL[256 + cc];
         if (a.draw.bias) lv[j] += bq[j];
       }
-      if constexpr (FILT) code = draw_core_filt<4>(lv, a.draw, b, t - 1, w == 0, false);
-      else code = draw_core<4>(lv, a.draw, b, t - 1, w == 0, false);
+      if constexpr (FILT) code = draw_core_filt<4, RP>(lv, a.draw, b, t - 1, w == 0, false);
+      else code = draw_core<4, RP>(lv, a.draw, b, t - 1, w == 0, false);
       if (s == n) {
         if (tr) tr[6] = wall_clock64();
         break;
@@ -489,15 +489,23 @@ LBWN_DEV void persist_head(const PersistK& a, int m, float* sm, int b0, int B, l
   }
 }
 
-// FILT: the chain blocks draw with draw_core_filt (the head blocks are the same code either way)
-template <bool LC, bool FILT>
+// FILT: the chain blocks draw with draw_core_filt (the head blocks are the same code either way).
+// RP: the instantiations of ring plans -- the draw stores by the local step mod R, and a stopped run (a
+// nonzero status since lbwn_gen_start: 7 from lbwn_gen_extend / lbwn_gen_collect) takes no step; every block
+// of the launch reads the word before any of them can have written it.  They are instantiations of their own
+// because this kernel's time follows its code layout: the plans without a ring keep the code
+// they had.
+template <bool LC, bool FILT, bool RP>
 __global__ __launch_bounds__(512) void gen_persist_kernel(PersistK a) {
   __shared__ __attribute__((aligned(16))) float sm[G_LDS];
+  if constexpr (RP) {
+    if (__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+  }
   const int per = a.Bg + P_NH, g = blockIdx.x / per, r = blockIdx.x % per;
   const int b0 = g * a.Bg, Bg = min(a.Bg, a.B - b0);
   long long* stepc = g ? a.gstep + (g - 1) : a.step;
   long long* trace = g ? nullptr : a.trace;
-  if (r < Bg) persist_chain<LC, FILT>(a, sm, b0 + r, stepc, trace);
+  if (r < Bg) persist_chain<LC, FILT, RP>(a, sm, b0 + r, stepc, trace);
   else if (r >= a.Bg) persist_head(a, r - a.Bg, sm, b0, Bg, stepc, trace);
   // (a ragged last group leaves chain slots r in [Bg, a.Bg) idle)
 }
@@ -512,6 +520,22 @@ __global__ void gen_decode_kernel(const int* __restrict__ samples, float* __rest
        e += (long long)gridDim.x * blockDim.x) {
     const long long i = (e / span) * max_steps + t0 + e % span;
     wav[i] = mu_decode_q(samples[i], Q);
+  }
+}
+
+// the same on a ring plan: stream b's steps [step - n, step) are its local steps t - base_b, each in column
+// (t - base_b) mod R (a begin lies between two runs, so base_b <= step - n; n > R decodes the survivors twice)
+__global__ void gen_decode_ring_kernel(const int* __restrict__ samples, float* __restrict__ wav, const long long* step,
+                                       const long long* sess, int B, unsigned R, int n, int Q) {
+  const long long t1 = *step, t0 = max(t1 - n, 0LL);
+  const long long span = t1 - t0;
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < (long long)B * span;
+       e += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(e / span);
+    const long long i = t0 + e % span - (sess ? sess[4 * b] : 0LL);
+    if (i < 0) continue;
+    const long c = (long)b * R + ring_col(i, R);
+    wav[c] = mu_decode_q(samples[c], Q);
   }
 }
 
@@ -539,13 +563,23 @@ int lbwn_gen_persist_run(lbwn_gen_plan* p, const lbwn_params* P, void* ws, int n
   const int nblk = p->pgroups * (p->pbg + P_NH);
   const bool lc = p->Lo > 0, filt = gen_filtered(p);
   if (lc) { k.lccond = gat<float>(ws, p->oLCC); k.NC = p->NC; }
-  (lc ? (filt ? gen_persist_kernel<true, true> : gen_persist_kernel<true, false>)
-      : (filt ? gen_persist_kernel<false, true> : gen_persist_kernel<false, false>))<<<nblk, 512, 0, st>>>(k);
+  const auto kern = p->ring ? (lc ? (filt ? gen_persist_kernel<true, true, true> : gen_persist_kernel<true, false, true>)
+                                  : (filt ? gen_persist_kernel<false, true, true> : gen_persist_kernel<false, false, true>))
+                            : (lc ? (filt ? gen_persist_kernel<true, true, false> : gen_persist_kernel<true, false, false>)
+                                  : (filt ? gen_persist_kernel<false, true, false> : gen_persist_kernel<false, false, false>));
+  kern<<<nblk, 512, 0, st>>>(k);
   LBWN_CHECK_LAUNCH();
   return 0;
 }
 
 int lbwn_gen_decode_launch(const lbwn_gen_plan* p, void* ws, int n_steps, hipStream_t st) {
+  if (p->ring) {
+    gen_decode_ring_kernel<<<std::max(1, std::min(1024, (int)(((long long)p->B * n_steps + 255) / 256))), 256, 0, st>>>(
+        gat<int>(ws, p->oSAMP), gat<float>(ws, p->oWAV), gat<long long>(ws, p->oSTEP),
+        p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr, p->B, (unsigned)p->ring, n_steps, p->Q);
+    LBWN_CHECK_LAUNCH();
+    return 0;
+  }
   gen_decode_kernel<<<std::max(1, std::min(1024, (int)(((long long)p->B * n_steps + 255) / 256))), 256, 0, st>>>(
       gat<int>(ws, p->oSAMP), gat<float>(ws, p->oWAV), gat<long long>(ws, p->oSTEP), p->B, p->max_steps, n_steps,
       p->Q);

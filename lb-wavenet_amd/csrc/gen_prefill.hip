@@ -310,6 +310,8 @@ static int prefill_check(const char* what, const lbwn_gen_plan* p, const lbwn_pa
   LBWN_REQUIRE(n >= 1, "%s: n must be >= 1 (got %lld)", what, (long long)n);
   LBWN_REQUIRE(ld_codes == 0 || ld_codes >= n, "%s: ld_codes %lld must be 0 (one shared vector) or >= n = %lld", what,
                (long long)ld_codes, (long long)n);
+  LBWN_REQUIRE(p->ring == 0, "%s: not supported on a ring plan (ring_steps = %lld): it is a whole-batch operation over "
+               "absolute steps", what, p->ring);
   LBWN_REQUIRE(!p->sess_mode, "%s: not supported in session mode (lbwn_gen_begin since lbwn_gen_start): it is a "
                "whole-batch operation", what);
   LBWN_REQUIRE(p->Lo == 0 || p->mel_loaded,

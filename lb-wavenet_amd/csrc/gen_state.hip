@@ -46,7 +46,8 @@ __global__ void gen_gc_proj_kernel(const float* emb, const float* gsig, const fl
 // the weight column coalesced over o and read once per 64 rows).  t and n_rows come from device words, so the launch is
 // capturable and a replayed graph follows a mel loaded later.
 // SESS (lbwn_gen_begin): every stream has its own region of "lc" (lc_stride rows apart) and its own
-// step origin and row count in the session words: r = min(max(t - base_b - 1, 0), rows_b - 1).
+// step origin and row count in the session words: r = min(max(t - base_b - 1, 0), rows_b - 1).  On a ring
+// plan the region holds Rlc rows and local row r lies at r mod Rlc (lbwn_gen_extend keeps rows_b ahead of r).
 constexpr int LCP_KT = 128;             // k tile staged per pass
 constexpr int LCP_RPT = LCP_ROWS / 4;   // rows per thread
 
@@ -55,6 +56,7 @@ struct LcProjK {
   const long long* step; const int* n_rows;
   int B, L, Lo, Cd, NC, n;
   const long long* sess; long lc_stride;   // SESS only
+  unsigned lc_ring;                        // SESS on a ring plan: Rlc, local row r lies at row r mod Rlc (0: at r)
 };
 
 template <bool SESS>
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256) void gen_lc_proj_kernel(LcProjK a) {
       const int m = min(m0 + tid, M - 1), b = m % a.B;
       const long long rows = max(a.sess[4 * b + 2], 1LL);
       const long long r = min(max(t0 + m / a.B - a.sess[4 * b] - 1, 0LL), rows - 1);
-      srow[tid] = (long)b * a.lc_stride + (long)r;
+      srow[tid] = (long)b * a.lc_stride + (a.lc_ring ? (long)ring_col(r, a.lc_ring) : (long)r);
     }
     __syncthreads();
   }
@@ -207,6 +209,63 @@ __global__ __launch_bounds__(256) void gen_begin_kernel(BeginK a) {
   }
 }
 
+// ---- feeding and draining a session while it runs (lbwn_gen_extend, lbwn_gen_collect) ----
+// The host cannot see a captured run's replays, so what depends on the step is checked here: plain compares
+// and one word store.  A refusal leaves "status" 7 (an earlier nonzero status stays) and changes nothing else.
+constexpr int GS_RANGE = 7;
+
+// The first launch of an extend: stream slot[i] gains add[i] rows.  cap = the rows its region holds; on a ring
+// plan the rows behind r, the row its current local step reads, are free again.  One block; a refusal of any
+// entry (or a run that is already stopped) advances none of the launch's words.
+struct ExtendK {
+  long long* sess; const long long* step; int* status;
+  long long cap;
+  int ring, n;
+  int slot[GB_MAX], add[GB_MAX];
+};
+
+__global__ __launch_bounds__(GB_MAX) void gen_extend_kernel(ExtendK a) {
+  const int i = threadIdx.x;
+  const int st0 = *a.status;
+  bool bad = st0 != 0;
+  if (i < a.n) {
+    const int b = a.slot[i];
+    const long long rows = a.sess[4 * b + 2], loc = *a.step - a.sess[4 * b];
+    const long long r = a.ring ? min(max(loc - 1, 0LL), rows) : 0LL;   // r = rows: every row given is read
+    bad |= rows + a.add[i] - r > a.cap;
+  }
+  if (__syncthreads_or(bad)) {
+    if (i == 0 && st0 == 0) *a.status = GS_RANGE;
+    return;
+  }
+  if (i < a.n) a.sess[4 * a.slot[i] + 2] += a.add[i];
+}
+
+// Local steps [i0, i0 + n) of stream b out of "samples" / "wav" [B][cols] into dense buffers (either may be
+// null).  e = the local steps already run; on a ring plan column = local step mod R and the range must not be
+// overwritten yet, else column = base + local step.  Every block decides for itself before it writes.
+struct CollectK {
+  const int* samples; const float* wav; const long long* step; const long long* sess; int* status;
+  int* samples_out; float* wav_out;
+  long long i0, n, cols;
+  unsigned ring;
+  int b;
+};
+
+__global__ __launch_bounds__(256) void gen_collect_kernel(CollectK a) {
+  const long long base = a.sess ? a.sess[4 * a.b] : 0LL, e = *a.step - base;
+  const bool ok = a.i0 + a.n <= e && (a.ring ? a.i0 >= e - (long long)a.ring : base + a.i0 + a.n <= a.cols);
+  if (!ok) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *a.status == 0) *a.status = GS_RANGE;
+    return;
+  }
+  for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < a.n; j += (long long)gridDim.x * blockDim.x) {
+    const long c = (long)a.b * a.cols + (a.ring ? (long)ring_col(a.i0 + j, a.ring) : (long)(base + a.i0 + j));
+    if (a.samples_out) a.samples_out[j] = a.samples[c];
+    if (a.wav_out) a.wav_out[j] = a.wav[c];
+  }
+}
+
 // ---- state snapshot (lbwn_gen_state_save / lbwn_gen_state_load) ----------------
 // What a run is between two launches: the rings, the pending codes, the step counter (and the
 // persistent groups' copies of it).  The snapshot is stream-major -- a 256-byte header, then per
@@ -321,8 +380,11 @@ extern "C" int lbwn_gen_start(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
   LBWN_REQUIRE(p->a.n_gc_embed == 0 || gc_ids, "gen_start: GC arch needs gc_ids [B]");
   LBWN_REQUIRE(!teacher || (n_teacher >= 0 && n_teacher <= p->max_teacher),
                "gen_start: teacher length %lld exceeds plan capacity %lld", (long long)n_teacher, p->max_teacher);
+  LBWN_REQUIRE(p->ring == 0 || !teacher || n_teacher == 0, "gen_start: n_teacher = %lld on a ring plan; the teacher "
+               "override is keyed by the absolute step and ring plans do not take it", (long long)n_teacher);
   hipStream_t st = (hipStream_t)stream;
   p->n_teacher = teacher ? n_teacher : 0;
+  std::fill(p->sess_rows.begin(), p->sess_rows.end(), 0LL);
   p->mel_loaded = false;
   p->sess_mode = false;
   p->n_begun = 0;
@@ -406,6 +468,7 @@ int lbwn_gen_lc_proj_launch(const lbwn_gen_plan* p, const lbwn_params* P, void* 
   k.step = gat<long long>(ws, p->oSTEP); k.n_rows = gat<int>(ws, p->oSTEP + 12);
   k.B = p->B; k.L = p->L; k.Lo = p->Lo; k.Cd = p->Cd; k.NC = p->NC; k.n = n;
   k.sess = p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr; k.lc_stride = (long)p->lc_rows;
+  k.lc_ring = p->ring ? (unsigned)p->lc_rows : 0u;
   const dim3 grid(p->L, (n * p->B + LCP_ROWS - 1) / LCP_ROWS);
   (p->sess_mode ? gen_lc_proj_kernel<true> : gen_lc_proj_kernel<false>)<<<grid, 256, 0, st>>>(k);
   LBWN_CHECK_LAUNCH();
@@ -475,6 +538,7 @@ extern "C" int lbwn_gen_begin(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
   p->sess_mode = true;
   for (int i = 0; i < n; ++i) {
     if (!p->sess_begun[s[i].slot]) { p->sess_begun[s[i].slot] = 1; ++p->n_begun; }
+    p->sess_rows[s[i].slot] = lc ? s[i].n_frames * p->hop : 0;
   }
   if (lc) {
     for (int i = 0; i < n; ++i) {   // the stream's own region of "lc" and of the stages' scratch
@@ -488,6 +552,94 @@ extern "C" int lbwn_gen_begin(lbwn_gen_plan* p, const lbwn_params* P, void* ws, 
       if (int e = gen_upsample(p, P, s[i].mel, s[i].n_frames, act, st)) return e;
     }
   }
+  return 0;
+}
+
+extern "C" int lbwn_gen_extend(lbwn_gen_plan* p, const lbwn_params* P, void* ws, const lbwn_gen_extend_entry* e, int n,
+                               size_t struct_size, void* stream) {
+  LBWN_REQUIRE(p, "gen_extend: plan is null");
+  LBWN_REQUIRE(P, "gen_extend: params is null");
+  LBWN_REQUIRE(ws, "gen_extend: workspace is null");
+  LBWN_REQUIRE(e, "gen_extend: e (the entry array) is null");
+  LBWN_REQUIRE(struct_size == sizeof(lbwn_gen_extend_entry), "gen_extend: struct_size %zu != %zu", struct_size,
+               sizeof(lbwn_gen_extend_entry));
+  LBWN_REQUIRE(n >= 1 && n <= p->B, "gen_extend: n = %d entries must be in 1..batch_sz = %d", n, p->B);
+  LBWN_REQUIRE(p->Lo > 0, "gen_extend: the arch has no local conditioning (no mel to extend)");
+  LBWN_REQUIRE(P->lc_sig && P->lc_gate, "gen_extend: LC_SIGNAL/LC_GATE pointers are null");
+  for (int i = 0; i < p->nup; ++i) LBWN_REQUIRE(P->lc_up[i], "gen_extend: LC_UPSAMPLE_%d pointer is null", i);
+  const long long max_frames = p->lc_rows / p->hop;
+  std::vector<unsigned char>& seen = p->sess_seen;
+  std::fill(seen.begin(), seen.end(), 0);
+  for (int i = 0; i < n; ++i) {
+    LBWN_REQUIRE(e[i].slot >= 0 && e[i].slot < p->B, "gen_extend: e[%d].slot = %d is outside [0, batch_sz = %d)", i,
+                 e[i].slot, p->B);
+    LBWN_REQUIRE(!seen[e[i].slot], "gen_extend: e[%d].slot = %d is listed twice", i, e[i].slot);
+    seen[e[i].slot] = 1;
+    LBWN_REQUIRE(e[i].mel, "gen_extend: e[%d].mel is null", i);
+    LBWN_REQUIRE((((uintptr_t)e[i].mel) & 15) == 0, "gen_extend: e[%d].mel %p is not 16-byte aligned", i,
+                 (const void*)e[i].mel);
+    LBWN_REQUIRE(e[i].n_frames >= 1 && e[i].n_frames <= max_frames,
+                 "gen_extend: e[%d].n_frames = %lld must be in 1..%lld (x hop %lld within the plan's %lld rows)", i,
+                 (long long)e[i].n_frames, max_frames, p->hop, p->lc_rows);
+  }
+  for (int i = 0; i < n; ++i) {   // what depends on the run, after what the entries alone decide
+    LBWN_REQUIRE(p->sess_mode && p->sess_begun[e[i].slot], "gen_extend: e[%d].slot = %d has begun no session since "
+                 "lbwn_gen_start (lbwn_gen_begin first)", i, e[i].slot);
+    LBWN_REQUIRE(p->ring || p->sess_rows[e[i].slot] + e[i].n_frames * p->hop <= p->lc_rows,
+                 "gen_extend: e[%d].n_frames = %lld: the session's %lld rows + %lld exceed the plan's %lld reserved rows",
+                 i, (long long)e[i].n_frames, p->sess_rows[e[i].slot], (long long)e[i].n_frames * p->hop, p->lc_rows);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < n; i0 += GB_MAX) {
+    ExtendK k;
+    memset(&k, 0, sizeof(k));
+    k.sess = gat<long long>(ws, p->oSESS); k.step = gat<long long>(ws, p->oSTEP); k.status = gat<int>(ws, p->oSTEP + 8);
+    k.cap = p->lc_rows; k.ring = p->ring != 0; k.n = std::min(GB_MAX, n - i0);
+    for (int i = 0; i < k.n; ++i) { k.slot[i] = e[i0 + i].slot; k.add[i] = (int)(e[i0 + i].n_frames * p->hop); }
+    gen_extend_kernel<<<1, GB_MAX, 0, st>>>(k);
+    LBWN_CHECK_LAUNCH();
+    // the mirror follows the words launch by launch, whatever the upsample launches below return
+    for (int i = 0; i < k.n; ++i) p->sess_rows[k.slot[i]] += k.add[i];
+  }
+  for (int i = 0; i < n; ++i) {
+    // frames [f0, f0 + n_frames) of the stream's region, the second piece from frame 0 where the ring wraps;
+    // every piece uses the head of the stream's stage scratch
+    const int b = e[i].slot;
+    const long long f0 = (p->sess_rows[b] / p->hop - e[i].n_frames) % max_frames;
+    float* act[8];
+    long long r = max_frames;
+    for (int j = 0; j + 1 < p->nup; ++j) {
+      r *= p->up[j];
+      act[j] = gat<float>(ws, p->oLCACT[j]) + (size_t)b * r * p->Lo;
+    }
+    for (long long done = 0; done < e[i].n_frames;) {
+      const long long f = (f0 + done) % max_frames, nf = std::min<long long>(e[i].n_frames - done, max_frames - f);
+      act[p->nup - 1] = gat<float>(ws, p->oLC) + ((size_t)b * p->lc_rows + (size_t)f * p->hop) * p->Lo;
+      if (int err = gen_upsample(p, P, e[i].mel + done * p->Li, nf, act, st)) return err;
+      done += nf;
+    }
+  }
+  return 0;
+}
+
+extern "C" int lbwn_gen_collect(lbwn_gen_plan* p, void* ws, int slot, int64_t i0, int64_t n, float* wav_out,
+                                int* samples_out, void* stream) {
+  LBWN_REQUIRE(p, "gen_collect: plan is null");
+  LBWN_REQUIRE(ws, "gen_collect: workspace is null");
+  LBWN_REQUIRE(slot >= 0 && slot < p->B, "gen_collect: slot = %d is outside [0, batch_sz = %d)", slot, p->B);
+  LBWN_REQUIRE(i0 >= 0, "gen_collect: i0 = %lld must be >= 0", (long long)i0);
+  LBWN_REQUIRE(n >= 0 && n <= INT64_MAX - i0, "gen_collect: n = %lld must be >= 0 (and i0 + n within int64)", (long long)n);
+  LBWN_REQUIRE(wav_out || samples_out, "gen_collect: wav_out and samples_out are both null");
+  if (n == 0) return 0;
+  CollectK k;
+  memset(&k, 0, sizeof(k));
+  k.samples = gat<int>(ws, p->oSAMP); k.wav = gat<float>(ws, p->oWAV); k.step = gat<long long>(ws, p->oSTEP);
+  k.sess = p->sess_mode ? gat<long long>(ws, p->oSESS) : nullptr; k.status = gat<int>(ws, p->oSTEP + 8);
+  k.samples_out = samples_out; k.wav_out = wav_out;
+  k.i0 = i0; k.n = n; k.cols = gen_out_cols(p); k.ring = (unsigned)p->ring; k.b = slot;
+  const int grid = (int)std::max<long long>(1, std::min<long long>(1024, (n + 255) / 256));
+  gen_collect_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(k);
+  LBWN_CHECK_LAUNCH();
   return 0;
 }
 
@@ -543,6 +695,8 @@ extern "C" int lbwn_gen_state_load(lbwn_gen_plan* p, void* ws, const void* state
   LBWN_REQUIRE(src_stream || state_streams == p->B,
                "gen_state_load: src_stream is null (identity) but state_streams %d != batch_sz %d", state_streams, p->B);
   LBWN_REQUIRE((((uintptr_t)state) & 15) == 0, "gen_state_load: state %p is not 16-byte aligned", state);
+  LBWN_REQUIRE(!(p->ring && p->sess_mode && p->Lo > 0), "gen_state_load: a ring LC plan in session mode: the rows the "
+               "rewound steps read may be overwritten and the row mirror is not carried");
   hipStream_t st = (hipStream_t)stream;
   StateK k = state_args(p, ws, const_cast<void*>(state));   // LOAD only reads it
   k.state_streams = state_streams;

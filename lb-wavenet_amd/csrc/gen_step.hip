@@ -348,15 +348,28 @@ LBWN_DEV int draw_wave(const DrawK& a, int b, long long t, bool write) {
   else return draw_core<MP>(v, a, b, t, write);
 }
 
+// Ring plans only (as in the persistent form): a stopped run (the status word, 8 bytes behind the step counter,
+// is nonzero since lbwn_gen_start: 7 from lbwn_gen_extend / lbwn_gen_collect) takes no step: the sampler, the last launch of a step, draws nothing and block 0 takes back the step's count (the
+// chain has moved the rings, which only lbwn_gen_start brings back, as it clears the status).  No block of
+// this launch reads the counter after that.
+LBWN_DEV bool sample_stopped(const long long* step) {
+  if (reinterpret_cast<const int*>(step)[2] == 0) return false;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_fetch_add(const_cast<long long*>(step), -1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
+}
+
 // the per-step path's sampler: one wave per stream; the step counter was advanced by this
 // step's skip GEMV, so this step is *step - 1
 __global__ __launch_bounds__(64) void gen_sample_kernel(DrawK a, const long long* step) {
+  if (a.ring && sample_stopped(step)) return;
   const long long t = *step - 1;
   if (a.Q > 256) draw_wave<8>(a, blockIdx.x, t, true);
   else draw_wave<4>(a, blockIdx.x, t, true);
 }
 // the same with the filtered draw (a second kernel, so the default sampler's code is untouched)
 __global__ __launch_bounds__(64) void gen_sample_filt_kernel(DrawK a, const long long* step) {
+  if (a.ring && sample_stopped(step)) return;
   const long long t = *step - 1;
   if (a.Q > 256) draw_wave<8, true>(a, blockIdx.x, t, true);
   else draw_wave<4, true>(a, blockIdx.x, t, true);

@@ -91,6 +91,11 @@ def get_args(argv=None):
                    help='(build extension) with --mel-list: the most the outputs, the upsampled mels and the '
                         'upsample stages\' scratch of one run may take on the device; a longer list is vocoded '
                         'in consecutive groups')
+    p.add_argument('--mel-list-ring', type=int, default=0, metavar='STEPS',
+                   help='(build extension) with --mel-list: vocode the whole list in one continuous schedule on a '
+                        'ring plan whose outputs and upsampled mels hold STEPS steps per stream (>= --chunk-size), '
+                        'whatever the list\'s length: no groups, --mel-list-budget-mb does not apply, and every '
+                        'wav is written as its utterance completes (0 = off)')
     p.add_argument('--temperature', type=float, default=1.0,
                    help='(build extension) softmax temperature of the draw, finite and > 0 (1 = off)')
     p.add_argument('--top-k', type=int, default=0,
@@ -226,15 +231,20 @@ def main_mel_list(args, arch):
     if not os.access(ckpt_file(args.ckpt), os.R_OK):
         print("Couldn't find checkpoint file {}".format(ckpt_file(args.ckpt)), file=stderr)
         sys.exit(1)
+    ring = int(args.mel_list_ring)
+    if ring < 0 or 0 < ring < args.chunk_size:
+        print('--mel-list-ring {}: must be 0 (off) or at least --chunk-size {}'.format(ring, args.chunk_size),
+              file=stderr)
+        sys.exit(1)
     hop = mel_hop_sz(arch)
     lengths = [m.shape[0] * hop for _, m, _ in utts]
-    groups = mel_list_groups(lengths, args.batch_size, args.chunk_size, arch['n_lc_out'], arch['lc_upsample'],
-                             int(args.mel_list_budget_mb * 2 ** 20))
+    groups = [] if ring else mel_list_groups(lengths, args.batch_size, args.chunk_size, arch['n_lc_out'],
+                                             arch['lc_upsample'], int(args.mel_list_budget_mb * 2 ** 20))
     net = WaveNetGen(arch['n_blocks'], arch['n_block_layers'], arch['n_quant'], arch['n_res'], arch['n_dil'],
                      arch['n_skip'], arch['n_post'], arch['n_gc_embed'], arch['n_gc_category'], arch['use_bias'],
                      args.batch_size, args.chunk_size, None, seed=args.seed, n_lc_in=arch['n_lc_in'],
                      n_lc_out=arch['n_lc_out'], lc_upsample=arch['lc_upsample'], temperature=args.temperature,
-                     top_k=args.top_k, top_p=args.top_p)
+                     top_k=args.top_k, top_p=args.top_p, ring_steps=ring)
     print('Restoring from {}'.format(args.ckpt))
     try:
         net.restore(args.ckpt, ema=args.ema)
@@ -245,6 +255,18 @@ def main_mel_list(args, arch):
         sys.exit(1)
     from scipy.io import wavfile
     os.makedirs(args.wav_dir, exist_ok=True)
+    if ring:
+        # one ring schedule for the whole list (WaveNetGen.vocode_iter): keys = the list positions, as below
+        print('Vocoding {} utterances in one ring schedule of {} steps.'.format(len(utts), ring))
+        wavs = [None] * len(utts)
+        gcs = [v for v, _, _ in utts] if arch['n_gc_embed'] else None
+        for u, w in net.vocode_iter((m for _, m, _ in utts), gc_ids=gcs):
+            wavs[u] = w.cpu().numpy().astype(np.float32)
+            path = os.path.join(args.wav_dir, utts[u][2] + '.wav')
+            wavfile.write(path, args.sample_rate, wavs[u])
+            print('Wrote {}'.format(path))
+        print('Finished.')
+        return wavs
     print('Vocoding {} utterances in {} group(s).'.format(len(utts), len(groups)))
     wavs = [None] * len(utts)
     for grp in groups:

@@ -119,6 +119,21 @@ class GenSession(ctypes.Structure):
     _fields_ = [('slot', c_int), ('gc_id', c_int), ('key', c_int64), ('mel', c_fp), ('n_frames', c_int64)]
 
 
+class GenPlanArgs(ctypes.Structure):
+    """lbwn_gen_plan_args (include/lbwn.h), field for field; struct_size is set on construction."""
+    _fields_ = [('struct_size', c_size_t), ('batch_sz', c_int), ('max_steps', c_int64), ('max_teacher', c_int64),
+                ('ring_steps', c_int64)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(GenPlanArgs)
+
+
+class GenExtendEntry(ctypes.Structure):
+    """lbwn_gen_extend_entry (include/lbwn.h), field for field."""
+    _fields_ = [('slot', c_int), ('mel', c_fp), ('n_frames', c_int64)]
+
+
 _SIGS = {
     'lbwn_mel_plan_create': (c_int, [ctypes.POINTER(MelCfg), ctypes.POINTER(c_void_p)]),
     'lbwn_mel_plan_destroy': (None, [c_void_p]),
@@ -159,6 +174,10 @@ _SIGS = {
     'lbwn_gen_is_persistent': (c_int, [c_void_p]),
     'lbwn_gen_begin': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(GenSession), c_int, c_size_t,
                                c_void_p]),
+    'lbwn_gen_plan_create_ex': (c_int, [ctypes.POINTER(Arch), ctypes.POINTER(GenPlanArgs), ctypes.POINTER(c_void_p)]),
+    'lbwn_gen_extend': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, ctypes.POINTER(GenExtendEntry), c_int,
+                                c_size_t, c_void_p]),
+    'lbwn_gen_collect': (c_int, [c_void_p, c_fp, c_int, c_int64, c_int64, c_fp, c_fp, c_void_p]),
     'lbwn_gen_prefill': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_void_p]),
     'lbwn_gen_score_scratch_bytes': (c_size_t, [c_void_p]),
     'lbwn_gen_score': (c_int, [c_void_p, ctypes.POINTER(Params), c_fp, c_fp, c_int64, c_int64, c_fp, c_int64, c_fp,

@@ -43,6 +43,13 @@ continue; ``take(slot, n)`` is a session's first n samples of "wav".  ``vocode(m
 different lengths into one wav each, recycling a stream as soon as its utterance is covered (the schedule of
 ``plan_sessions``); with the default keys (the utterance indices) the result does not depend on batch_sz or
 on the schedule.
+
+Ring plans (keyword-only ``ring_steps=R``; lbwn_gen_plan_create_ex): "samples" / "wav" hold the last
+R local steps of every stream and "lc" a ring of ceil(R/hop)·hop rows, so the workspace does not grow with the
+run.  ``extend(slots, mels)`` feeds a live session more frames, ``collect(slot, i0, n)`` copies local steps out
+of the rings, ``take`` returns a collected copy; ``vocode`` runs the schedule of ``plan_ring`` and
+``vocode_iter(iterable)`` yields (index, wav) as utterances finish, endlessly if the iterable is.  Prefill,
+score and a teacher vector are refused on a ring plan.
 """
 import ctypes
 import math
@@ -118,6 +125,99 @@ def plan_sessions(lengths, batch_sz, chunk):
     return rounds, total
 
 
+def _check_ring_args(batch_sz, chunk, ring_steps, hop):
+    for name, v in (('batch_sz', batch_sz), ('chunk', chunk), ('ring_steps', ring_steps), ('hop', hop)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('plan_ring: %s must be an integer >= 1, got %r' % (name, v))
+    if chunk > ring_steps:
+        raise ValueError('plan_ring: chunk = %d exceeds ring_steps = %d (a round would overwrite its own samples '
+                         'before they are collected)' % (chunk, ring_steps))
+
+
+def ring_rounds(lengths, batch_sz, chunk, ring_steps, hop):
+    """``plan_ring``'s rounds as a generator over an iterator of lengths, which is read one utterance ahead of
+    the slots (to know whether any waits, as ``plan_sessions`` does): an endless iterator gives an endless
+    schedule."""
+    _check_ring_args(batch_sz, chunk, ring_steps, hop)
+    B, chunk, R, hop = int(batch_sz), int(chunk), int(ring_steps), int(hop)
+    Rlc = -(-R // hop) * hop
+    it = iter(lengths)
+    state = {'u': 0}
+
+    def pull():
+        try:
+            n = int(next(it))
+        except StopIteration:
+            return None
+        if n < 1:
+            raise ValueError('plan_ring: lengths[%d] = %d must be >= 1' % (state['u'], n))
+        return n
+
+    ahead = pull()
+    # per slot: the utterance, its length, frames, local steps run, rows fed, samples collected
+    sess = [None] * B
+    left = [0] * B
+    while True:
+        begins = []
+        for slot in range(B):
+            if left[slot] <= 0 and ahead is not None:
+                n, u = ahead, state['u']
+                state['u'] += 1
+                ahead = pull()
+                nf = min(-(-n // hop), Rlc // hop)
+                sess[slot] = dict(u=u, len=n, frames=-(-n // hop), i=0, rows=nf * hop)
+                begins.append((slot, u, nf))
+                left[slot] = n
+        need = max(left)
+        if need <= 0:
+            return
+        todo = chunk if ahead is not None else min(chunk, need)
+        left = [r - todo for r in left]
+        while todo > 0:
+            # feed every live session what its ring takes: the rows behind the one its next step reads are free
+            extends, can = [], todo
+            for slot, s in enumerate(sess):
+                if s is None or s['i'] >= s['len']:
+                    continue       # no session, or past its end: the clamp is the rule there
+                full = s['frames'] * hop
+                rows = min(full, (max(s['i'] - 1, 0) // hop) * hop + Rlc)
+                if rows > s['rows']:
+                    extends.append((slot, s['u'], s['rows'] // hop, (rows - s['rows']) // hop))
+                    s['rows'] = rows
+                if s['rows'] < full:          # local step j reads row j - 1: steps up to j = rows may run
+                    can = min(can, s['rows'] - s['i'] + 1)
+            steps = min(can, R)
+            collects = []
+            for slot, s in enumerate(sess):
+                if s is None:
+                    continue
+                lo, hi = min(s['i'], s['len']), min(s['i'] + steps, s['len'])
+                s['i'] += steps
+                if hi > lo:
+                    collects.append((slot, s['u'], lo, hi - lo))
+            yield steps, begins, extends, collects
+            begins = []
+            todo -= steps
+
+
+def plan_ring(lengths, batch_sz, chunk, ring_steps, hop):
+    """``plan_sessions`` for a ring plan of ``ring_steps`` = R columns and Rlc = ceil(R/hop)·hop rows per stream:
+    the same deal of utterances to slots at the same chunk boundaries and the same total, each round with
+    what a ring needs around it.  Returns (rounds, total); a round is (steps, begins, extends, collects):
+      begins   [(slot, utterance, n_frames)]        begin with the utterance's first n_frames frames
+      extends  [(slot, utterance, f0, n_frames)]    then extend with its frames [f0, f0 + n_frames)
+      collects [(slot, utterance, i0, n)]           after the steps, collect its local steps [i0, i0 + n)
+    A round of ``plan_sessions`` is cut into several where a session's rows run out before the round ends (an
+    utterance longer than the ring is begun with what fits and extended round by round; only the first
+    piece carries the begins).  Guaranteed: no round runs more than R steps; no session ever holds more than
+    Rlc rows beyond the one its next step reads; no step runs before its mel row is fed, except past an
+    utterance's end, where the last row is repeated (the per-session clamp); every sample of every
+    utterance is collected exactly once, in order, right after the round that drew it.  ValueError naming
+    the argument for what cannot be scheduled (chunk > ring_steps).  Pure host arithmetic."""
+    rounds = list(ring_rounds([int(n) for n in lengths], batch_sz, chunk, ring_steps, hop))
+    return rounds, sum(r[0] for r in rounds)
+
+
 class GenState:
     """A snapshot written by lbwn_gen_state_save: ``blob`` is the uint8 tensor in the documented layout
     (256-byte header, then n_streams stream-major records), ``dims`` the arch dimensions it belongs to."""
@@ -161,7 +261,10 @@ class WaveNetGen:
     def __init__(self, n_blocks, n_block_layers, n_quant, n_res, n_dil, n_skip, n_post1, n_gc_embed,
                  n_gc_category, use_bias, batch_sz, chunk_sz, teacher_vec=None, *, pre_bias=True, seed=0,
                  device='cuda', graph=True, n_lc_in=0, n_lc_out=0, lc_upsample=(), temperature=1.0, top_k=0,
-                 top_p=1.0):
+                 top_p=1.0, ring_steps=0):
+        if isinstance(ring_steps, bool) or not isinstance(ring_steps, (int, np.integer)) or ring_steps < 0:
+            raise ValueError('ring_steps must be an integer >= 0, got %r' % (ring_steps,))
+        self.ring_steps = int(ring_steps)     # > 0: a ring plan (lbwn_gen_plan_create_ex); max_steps is then R
         self.sampling = self._check_sampling(temperature, top_k, top_p)
         self.arch = normalize_arch(dict(n_blocks=n_blocks, n_block_layers=n_block_layers, n_quant=n_quant,
                                         n_res=n_res, n_dil=n_dil, n_skip=n_skip, n_post=n_post1,
@@ -204,6 +307,7 @@ class WaveNetGen:
         self._hstep = 0                  # the device step counter, tracked on the host (None: unknown)
         self._base = [None] * self.batch_sz   # each slot's step origin
         self._sess_mels = {}             # slot -> the device mel its upsample launches read
+        self._rows = [0] * self.batch_sz      # each slot's rows given by begin and extend (the plan's mirror)
 
     # ---- parameters -------------------------------------------------------------------------
     def load_params(self, src, ema=False):
@@ -249,8 +353,16 @@ class WaveNetGen:
         self._arch_c = a
         h = ctypes.c_void_p()
         n_teach = 0 if self.teacher_mu is None else self.teacher_mu.numel()
-        _lib.check(self.lib.lbwn_gen_plan_create(ctypes.byref(a), self.batch_sz, int(max_steps), int(n_teach),
-                                                 ctypes.byref(h)))
+        if self.ring_steps:
+            # a ring plan: "samples" / "wav" hold ring_steps columns whatever the run's length (max_steps, the
+            # column count of samples() and of the wav view, is the ring's)
+            args = _lib.GenPlanArgs(batch_sz=self.batch_sz, max_steps=1, max_teacher=int(n_teach),
+                                    ring_steps=self.ring_steps)
+            _lib.check(self.lib.lbwn_gen_plan_create_ex(ctypes.byref(a), ctypes.byref(args), ctypes.byref(h)))
+            max_steps = self.ring_steps
+        else:
+            _lib.check(self.lib.lbwn_gen_plan_create(ctypes.byref(a), self.batch_sz, int(max_steps), int(n_teach),
+                                                     ctypes.byref(h)))
         self._plan = h
         self.max_steps = int(max_steps)
         nbytes = self.lib.lbwn_gen_workspace_bytes(h)
@@ -601,6 +713,9 @@ class WaveNetGen:
         ``prefill='fanout'``: as True, the prompt prefilled once per distinct voice id (``init_buffers``).
         ``prefill='score'``: as True, and ``teacher_logp`` holds the teacher's log-probabilities."""
         self._check_prefill(prefill, mel)
+        if self.ring_steps and gen_sz > self.ring_steps:
+            raise ValueError('run: gen_sz %d exceeds ring_steps %d (a ring plan returns its last ring_steps samples '
+                             'through collect)' % (gen_sz, self.ring_steps))
         mel_in = mel
         mel = self._check_mel(mel, int(gen_sz))
         if self._plan is None or self.max_steps < gen_sz:
@@ -619,6 +734,8 @@ class WaveNetGen:
         s = int(self.tensor('status', torch.int32).item())
         if s == 6:
             raise RuntimeError('generation status 6: load_state refused the snapshot or the stream map')
+        if s == 7:
+            raise RuntimeError('generation status 7: the device refused the range of an extend or a collect')
         if s != 0:
             raise RuntimeError('generation status %d: a skip-helper hand-off timed out' % s)
 
@@ -735,15 +852,106 @@ class WaveNetGen:
         if not self._sess_mode:
             self._graph = None
             self._sess_mode = True
-        for b in slots:
+        for i, b in enumerate(slots):
             self._base[b] = self._hstep
+            self._rows[b] = 0 if mels[i] is None else int(mels[i].shape[0]) * self.hop
         return self
+
+    def _local_step(self, slot):
+        """The local steps stream ``slot`` has run, from the host's step mirror (read from the device once after
+        a load_state)."""
+        if self._hstep is None:
+            self._hstep = int(self.tensor('step', torch.int64).item())
+        return self._hstep - (self._base[slot] or 0)
+
+    @property
+    def lc_ring_rows(self):
+        """Rows of one stream's region of "lc": Rlc = ceil(R/hop)·hop on a ring plan, the reserved rows else."""
+        return -(-self.max_steps // self.hop) * self.hop if self.hop else 0
+
+    def extend(self, slots, mels):
+        """Append more mel frames to the live sessions of ``slots`` (lbwn_gen_extend, on the current stream):
+        ``mels[i]`` [n_frames, n_lc_in] are the frames after those the stream already has.  What the device
+        guards is refused here first, from the host's step mirror: on a ring plan a session may hold at most
+        Rlc rows beyond the one its next step reads, elsewhere at most the reserved rows; ValueError."""
+        if self.arch['n_lc_out'] == 0:
+            raise ValueError('extend: the arch has no local conditioning (no mel to extend)')
+        try:
+            slots, mels = list(slots), list(mels)
+        except TypeError:
+            raise ValueError('extend: slots and mels must be lists, got %r and %r' % (slots, mels))
+        n = len(slots)
+        if not 1 <= n <= self.batch_sz:
+            raise ValueError('extend: %d slots given, expected 1..batch_sz = %d' % (n, self.batch_sz))
+        if len(mels) != n:
+            raise ValueError('extend: mels has %d entries for %d slots' % (len(mels), n))
+        for i, b in enumerate(slots):
+            if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch_sz:
+                raise ValueError('extend: slots[%d] = %r is not an integer in [0, %d)' % (i, b, self.batch_sz))
+            if self._plan is None or self._base[b] is None:
+                raise ValueError('extend: slots[%d] = %d has begun no session' % (i, b))
+        if len(set(int(b) for b in slots)) != n:
+            raise ValueError('extend: slots %r lists a stream twice' % (slots,))
+        mels = [self._as_mel(m, 'extend: mels[%d]' % i) for i, m in enumerate(mels)]
+        cap = self.lc_ring_rows
+        for i, b in enumerate(slots):
+            add, rows = int(mels[i].shape[0]) * self.hop, self._rows[b]
+            read = min(max(self._local_step(b) - 1, 0), rows) if self.ring_steps else 0
+            if rows + add - read > cap:
+                raise ValueError('extend: mels[%d] brings %d rows to the %d of stream %d, %d of them read: more than '
+                                 'the %d its region holds' % (i, add, rows, b, read, cap))
+        arr = (_lib.GenExtendEntry * n)()
+        keep = []
+        for i, b in enumerate(slots):
+            m = mels[i]
+            if not isinstance(m, torch.Tensor):
+                m = torch.from_numpy(np.ascontiguousarray(m, np.float32))
+            m = m.to(device=self.device, dtype=torch.float32).contiguous()
+            if m.data_ptr() % 16:
+                m = m.clone()
+            keep.append(m)
+            arr[i].slot, arr[i].mel, arr[i].n_frames = int(b), m.data_ptr(), m.shape[0]
+        _lib.check(self.lib.lbwn_gen_extend(self._plan, ctypes.byref(self._params_c), self._ws.data_ptr(), arr, n,
+                                            ctypes.sizeof(_lib.GenExtendEntry), _lib.stream_ptr()))
+        for i, b in enumerate(slots):
+            self._rows[b] += int(keep[i].shape[0]) * self.hop
+            self._sess_mels[(int(b), 'ext')] = keep[i]     # read by the upsample launches in stream order
+        return self
+
+    def collect(self, slot, i0, n):
+        """Local steps [i0, i0 + n) of stream ``slot`` as dense copies (wav float32 [n], samples int32 [n]) on
+        the device (lbwn_gen_collect, on the current stream).  The steps must have run and, on a ring plan,
+        lie within the last ring_steps of them; ValueError otherwise (the device guards the same)."""
+        if self._plan is None or isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or \
+                not 0 <= slot < self.batch_sz:
+            raise ValueError('collect: slot %r is not a stream of a built plan' % (slot,))
+        if isinstance(i0, bool) or not isinstance(i0, (int, np.integer)) or i0 < 0:
+            raise ValueError('collect: i0 must be an integer >= 0, got %r' % (i0,))
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError('collect: n must be an integer >= 0, got %r' % (n,))
+        e = self._local_step(slot)
+        if i0 + n > e:
+            raise ValueError('collect: steps [%d, %d) of stream %d: only %d have run' % (i0, i0 + n, slot, e))
+        if self.ring_steps and i0 < e - self.ring_steps:
+            raise ValueError('collect: i0 = %d of stream %d is overwritten: %d steps have run and the ring holds '
+                             'the last %d' % (i0, slot, e, self.ring_steps))
+        if not self.ring_steps and (self._base[slot] or 0) + i0 + n > self.max_steps:
+            raise ValueError('collect: steps [%d, %d) of stream %d lie past max_steps %d' % (i0, i0 + n, slot,
+                                                                                            self.max_steps))
+        wav = torch.empty(int(n), dtype=torch.float32, device=self.device)
+        smp = torch.empty(int(n), dtype=torch.int32, device=self.device)
+        if n:
+            _lib.check(self.lib.lbwn_gen_collect(self._plan, self._ws.data_ptr(), int(slot), int(i0), int(n),
+                                                 wav.data_ptr(), smp.data_ptr(), _lib.stream_ptr()))
+        return wav, smp
 
     def take(self, slot, n):
         """The first n samples of the session stream ``slot`` carries: "wav" columns base .. base + n - 1
-        (a view; the steps must have run)."""
+        (a view; the steps must have run).  On a ring plan a collected copy (they must still be in the ring)."""
         if self._plan is None or not 0 <= slot < self.batch_sz or self._base[slot] is None:
             raise ValueError('take: stream %r has begun no session' % (slot,))
+        if self.ring_steps:
+            return self.collect(slot, 0, n)[0]
         b0 = self._base[slot]
         if n < 0 or b0 + n > self.max_steps:
             raise ValueError('take: %d samples from step %d exceed max_steps %d' % (n, b0, self.max_steps))
@@ -770,6 +978,11 @@ class WaveNetGen:
                 raise ValueError('vocode: GC arch, gc_ids (one voice id per mel) required')
             gc_ids = [int(v) for v in gc_ids]
         mels = [self._as_mel(m, 'vocode: mels[%d]' % u) for u, m in enumerate(mels)]
+        if self.ring_steps:       # one continuous ring schedule (plan_ring), whatever the list's length
+            out = [None] * n_utt
+            for u, wav in self.vocode_iter(mels, gc_ids, keys, chunk):
+                out[u] = wav
+            return out
         lengths = [int(m.shape[0]) * self.hop for m in mels]
         rounds, total = plan_sessions(lengths, self.batch_sz, chunk)
         if self._plan is None or self.max_steps < total:
@@ -778,6 +991,81 @@ class WaveNetGen:
         self.chunk_sz = chunk
         try:
             return self._vocode_rounds(mels, gc_ids, keys, lengths, rounds)
+        finally:
+            self.chunk_sz = keep_chunk
+
+    def vocode_iter(self, mels, gc_ids=None, keys=None, chunk=None, samples=False):
+        """``vocode`` on a ring plan (``ring_steps`` > 0) as a generator over any iterable of mels: yields
+        (index, wav) as utterances finish, in the order they finish ((index, wav, µ-law codes) with
+        ``samples=True``).  ``gc_ids`` / ``keys`` are iterables
+        parallel to ``mels`` (keys default to the indices).  The schedule is ``ring_rounds``: an utterance
+        longer than the ring is begun with what fits and extended round by round, every round's samples are
+        collected right after it.  At most batch_sz utterances are in flight, plus the one read ahead, so an
+        endless iterable runs endlessly in the plan's fixed workspace."""
+        if self.arch['n_lc_out'] == 0:
+            raise ValueError('vocode_iter: the arch has no local conditioning (nothing to vocode from)')
+        if not self.ring_steps:
+            raise ValueError('vocode_iter: needs a ring plan (WaveNetGen(..., ring_steps=R))')
+        chunk = self.chunk_sz if chunk is None else int(chunk)
+        _check_ring_args(self.batch_sz, chunk, self.ring_steps, self.hop)
+        gc = self.arch['n_gc_embed'] > 0
+        if gc and gc_ids is None:
+            raise ValueError('vocode_iter: GC arch, gc_ids (one voice id per mel) required')
+        git = iter(gc_ids) if gc else None
+        kit = iter(keys) if keys is not None else None
+        live = {}                      # utterance -> dict(mel on the device, voice, key, length, parts)
+
+        def lengths():
+            for u, m in enumerate(mels):
+                m = self._as_mel(m, 'vocode: mels[%d]' % u)
+                if not isinstance(m, torch.Tensor):
+                    m = torch.from_numpy(np.ascontiguousarray(m, np.float32))
+                m = m.to(device=self.device, dtype=torch.float32).contiguous()
+                try:
+                    live[u] = dict(mel=m, gc=int(next(git)) if gc else 0, key=int(next(kit)) if kit else u,
+                                   len=int(m.shape[0]) * self.hop, parts=[])
+                except StopIteration:
+                    raise ValueError('vocode: gc_ids / keys are shorter than mels (at utterance %d)' % u)
+                yield live[u]['len']
+
+        if self._plan is None:
+            self.build_graph(self.ring_steps)
+        keep_chunk = self.chunk_sz       # ``chunk`` holds for this call only (step re-captures on a change)
+        self.chunk_sz = chunk
+        try:
+            self.init_sessions()
+            idle = np.zeros((1, self.arch['n_lc_in']), np.float32)   # streams no utterance has reached yet
+            first = True
+            for steps, begins, extends, collects in ring_rounds(lengths(), self.batch_sz, chunk, self.ring_steps,
+                                                                self.hop):
+                slots = [s for s, _, _ in begins]
+                ms = [live[u]['mel'][:nf] for _, u, nf in begins]
+                ks = [live[u]['key'] for _, u, _ in begins]
+                gs = [live[u]['gc'] for _, u, _ in begins] if gc else None
+                if first:
+                    first = False
+                    for s in range(self.batch_sz):
+                        if s not in slots:
+                            slots.append(s)
+                            ms.append(idle)
+                            ks.append(0)
+                            if gc:
+                                gs.append(0)
+                if slots:
+                    self.begin(slots, ms, gs, ks)
+                if extends:
+                    self.extend([s for s, _, _, _ in extends], [live[u]['mel'][f0:f0 + nf] for _, u, f0, nf in extends])
+                self.step(steps)
+                done = []
+                for s, u, i0, n in collects:
+                    live[u]['parts'].append(self.collect(s, i0, n))
+                    if i0 + n == live[u]['len']:
+                        done.append((u, live.pop(u)['parts']))
+                if done:
+                    self.check_status()       # one synchronisation per round that finishes an utterance
+                for u, parts in done:
+                    out = tuple(torch.cat([p[k] for p in parts]) for k in ((0, 1) if samples else (0,)))
+                    yield (u,) + out
         finally:
             self.chunk_sz = keep_chunk
 
